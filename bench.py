@@ -9,9 +9,23 @@ L=50, 80 classes) on N MI355X GPUs of one node.
 One process per GPU; weak scaling (4 images per GPU at every N); rank 0 prints ONE JSON
 line.  A step = forward + intertwiner (OT) loss + backward + gradient all-reduce + clip
 + SGD update on one synthetic COCO-shaped batch already resident in HBM (synthetic.py).
-All arithmetic is fp32, as in the reference.
+All arithmetic is fp32, as in the reference.  Every step starts from the same weights,
+momentum and intertwiner history (StepStart): the same arguments give the same results to
+rounding in every run.
 
-Extra objects on the JSON line
+A plain run sets up, warms up, times the K steps and prints the headline (metric, value, unit,
+higher_is_better, dtype, ms_per_step, losses).  Everything else it can measure or check runs
+only with --full, after the timed steps.
+
+    --dump-outputs DIR   after the timed steps, what the last timed step computed, as float32
+                         .npy files (dump_outputs()); the inputs are seeded, so two builds run
+                         with the same arguments can be compared output for output
+    --full               the objects below, the dense-backward reference and check, the
+                         configs[4] slice, the 2-image eager / hipGraph comparison, the host
+                         issue profile, the data-parallel overlap and configs[3] passes, the
+                         CPU baselines (--no-* options switch single parts off)
+
+Extra objects on the JSON line (--full)
   roofline      for crop_fwd_kernel<7, 7> (RoIAlign 7x7, the north-star kernel): algorithmic
                 bytes (SURVEY 8d's B_min = output + unique taps per RoI + box records) of its
                 launch in the step / its mean duration, measured with HIP events recorded on
@@ -496,10 +510,10 @@ def issue_profile(step, dev, ms_per_step_unprofiled, steps=2):
 
 
 def graph_ab_child():
-    """`python bench.py --batch-per-gpu 2 --graph-ab-child` in a process of its own; its JSON line."""
+    """`python bench.py --batch-per-gpu 2 --graph-ab-child --full` in a process of its own; its JSON line."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--batch-per-gpu", "2", "--graph-ab-child", "--no-cpu-baseline",
-           "--no-pmc", "--no-dense-reference", "--steps", "8", "--warmup", "3"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--batch-per-gpu", "2", "--graph-ab-child", "--full",
+           "--no-cpu-baseline", "--no-pmc", "--no-dense-reference", "--steps", "8", "--warmup", "3"]
     try:
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=400)
         lines = [l for l in r.stdout.decode("utf-8", "replace").splitlines() if l.startswith("{")]
@@ -567,8 +581,73 @@ def graph_ab_two_images(model, opt, dev, image_size, train_step, steps=8, own_mo
         out["error"] = repr(ex)
     model.external_proposals, model.generator = keep_ext, keep_gen
     out["what"] = ("2 images per GPU (BASELINE configs[3]'s per-rank shape) on one GPU, in a process of its own "
-                   "(python bench.py --batch-per-gpu 2 --graph-ab-child): eager launches vs one hipGraph replay of the whole step")
+                   "(python bench.py --batch-per-gpu 2 --graph-ab-child --full): eager launches vs one hipGraph replay of the whole step")
     return out
+
+
+class StepStart(object):
+    """The model and optimiser state before the first step, put back at the start of every step: each warm-up and
+    timed step is then the same train step (forward, losses, backward, clip, SGD update) from the same weights,
+    momentum and intertwiner history, on the draws of its turn (seeded).  Without it the W + K steps would form a
+    training trajectory, and the float atomics of the backward pass (summation order differs from run to run) would
+    steer it -- through the RoIs that follow the weights -- to results that differ between runs far beyond rounding.
+    Everything is restored in place (the tensors keep their addresses, as the SGD descriptor cache and a captured step
+    need); copy_ bumps the weights' versions, so the weight-derived caches of conv.py refresh as after an update.
+    The destinations are looked up at every restore: the forward pass may give a weight new storage (conv.py stores
+    convolution weights channels-last), which an alias taken earlier would no longer see."""
+
+    def __init__(self, model, opt):
+        from feature_intertwiner_amd import conv as ficonv
+        self.model, self.opt = model, opt
+        with torch.no_grad():
+            ficonv.prepare_step(model)          # the weights' final layout first: the copies then share their strides
+            self.src = [t.detach().clone() for t in model.state_dict(keep_vars=True).values()]
+
+    @torch.no_grad()
+    def restore(self):
+        groups = {}
+        for t, s in zip(self.model.state_dict(keep_vars=True).values(), self.src):
+            dst, src = groups.setdefault(t.dtype, ([], []))
+            dst.append(t)
+            src.append(s)
+        for dst, src in groups.values():
+            torch._foreach_copy_(dst, src)
+        # momentum buffers and the history buffer are created as zeros at their first use
+        bufs = [st["momentum_buffer"] for st in self.opt.state.values() if st.get("momentum_buffer") is not None]
+        if bufs:
+            torch._foreach_zero_(bufs)
+        fb = self.model.feature_buffer
+        if fb is not None:
+            fb.buffer.zero_()
+            fb.buffer_cnt.zero_()
+
+
+def dump_outputs(path, model, terms, sample=1 << 21, seed=2024):
+    """--dump-outputs DIR: what the caller of train_step holds after the LAST timed step, as float32 .npy files
+    (about 8 MB in all at the headline size):
+      loss_<term>.npy     each loss term train_step returned (shape [1])
+      params_sample.npy   the parameters after the step's update: all of model.named_parameters() flattened and
+                          concatenated in that order, `sample` positions drawn once per stride of total / sample
+                          (np.random.RandomState(seed)), the whole vector if it is shorter
+    Every step starts from the same state (StepStart), so runs with the same arguments agree to rounding."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in terms.items():
+        val = torch.as_tensor(v).detach().float().reshape(1).cpu().numpy()
+        np.save(os.path.join(path, "loss_%s.npy" % k), val.astype(np.float32))
+    params = [p for _, p in model.named_parameters()]
+    total = sum(p.numel() for p in params)
+    if total <= sample:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        stride = total / float(sample)
+        rs = np.random.RandomState(seed)
+        idx = np.minimum((np.arange(sample) * stride + rs.random_sample(sample) * stride).astype(np.int64), total - 1)
+    idx = torch.from_numpy(idx).to(params[0].device)
+    with torch.no_grad():
+        flat = torch.cat([p.detach().reshape(-1).float() for p in params])
+        np.save(os.path.join(path, "params_sample.npy"), flat[idx].cpu().numpy().astype(np.float32))
+    del flat
 
 
 def _self_launch(n):
@@ -698,6 +777,13 @@ def _main():
                     help="cfg3 = BASELINE configs[2], the headline (default); cfg5 = the single-GPU slice of BASELINE "
                          "configs[4]: 1333x800 padded to 1344^2, 2 images/GPU, 1000 RoIs/image + mask head, bf16 MFMA convs")
     ap.add_argument("--conv-precision", default=None, choices=["fp32", "bf16", "fp16"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, every further measurement and check of the JSON line (profiled pass and "
+                         "roofline objects, PMC traffic, dense-backward reference and check, configs[4] slice, issue "
+                         "profile, 2-image hipGraph A/B, data-parallel overlap and configs[3] passes, CPU baselines); "
+                         "the --no-* options below switch parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (float32; see dump_outputs())")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dense-reference", action="store_true",
                     help="skip the 8 extra steps (after the timed region) that time the dense form of the backward pass")
@@ -781,7 +867,10 @@ def _main():
     model.external_proposals = SyntheticProposals(batch[2], args.image_size, seed=7 + rank, cycle=16)
     model.generator = torch.Generator(device=dev).manual_seed(11 + rank)
 
+    start = StepStart(model, opt)
+
     def step():
+        start.restore()
         return train_step(model, opt, list(batch), do_meta=True, grad_sync=sync, world_size=world,
                           reduce_fn=reduce_fn)
 
@@ -855,11 +944,13 @@ def _main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    if sync is not None:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, terms)
+    if sync is not None and args.full:
         sync.check()               # replicas stayed consistent (host sync, outside the timed region)
     # ---- host issue time / GPU busy and idle time / launches per step, this rank (outside the timed region) ----------
     issue = None
-    if not args.no_issue_profile:
+    if args.full and not args.no_issue_profile:
         try:
             issue = issue_profile(step, dev, elapsed / args.steps * 1e3)
         except Exception as ex:
@@ -873,42 +964,44 @@ def _main():
         return json.dumps(out)
     # ---- a separate profiled pass for the roofline objects (HIP events around every library kernel) --
     prof_steps = max(1, args.profile_steps)
-    _lib.prof_reset()
-    _lib.prof_enable(True)
-    car.LAUNCH_LOG = []
-    ficonv.FLOP_LOG = {}
-    ficonv.SHAPE_LOG = []
-    # EXCLUSIVE kernel durations: in the timed region the weight gradients run on a second stream next to the data
-    # gradients (conv.WGRAD_SIDE_STREAM_MAX_PIXELS) and two kernels that share the chip each take longer than alone;
-    # the roofline objects price a kernel against the whole chip, so this pass keeps everything on one stream
-    # (`exclusive_ms_per_step` in the JSON is what that costs; `value` comes from the timed region above)
-    side_pixels = ficonv.WGRAD_SIDE_STREAM_MAX_PIXELS
-    ficonv.WGRAD_SIDE_STREAM_MAX_PIXELS = 0
-    from feature_intertwiner_amd import model as fimodel
-    dead_side = fimodel._DEAD_SIDE
-    fimodel._DEAD_SIDE = False            # the mask head's unread batch back on the main stream, for the same reason
-    from feature_intertwiner_amd import sub_module as fisub, workflow as fiwork
-    keep_side = (fimodel._PROPOSAL_SIDE, fisub._BIG_SIDE, fiwork.META_SIDE_STREAM)
-    fimodel._PROPOSAL_SIDE = fisub._BIG_SIDE = fiwork.META_SIDE_STREAM = False     # (round 4's side-stream work as well)
-    t1 = time.perf_counter()
-    for _ in range(prof_steps):
-        step()
-    torch.cuda.synchronize()
-    prof_elapsed = time.perf_counter() - t1
-    ficonv.WGRAD_SIDE_STREAM_MAX_PIXELS = side_pixels
-    fimodel._DEAD_SIDE = dead_side
-    fimodel._PROPOSAL_SIDE, fisub._BIG_SIDE, fiwork.META_SIDE_STREAM = keep_side
-    _lib.prof_enable(False)
-    log = car.LAUNCH_LOG
-    car.LAUNCH_LOG = None
-    flop_log = ficonv.FLOP_LOG
-    ficonv.FLOP_LOG = None
-    shape_log = ficonv.SHAPE_LOG
-    ficonv.SHAPE_LOG = None
-    shape_log = shape_log[:len(shape_log) // prof_steps]       # the convolutions of ONE step
+    log = flop_log = shape_log = prof_elapsed = None
+    if args.full:
+        _lib.prof_reset()
+        _lib.prof_enable(True)
+        car.LAUNCH_LOG = []
+        ficonv.FLOP_LOG = {}
+        ficonv.SHAPE_LOG = []
+        # EXCLUSIVE kernel durations: in the timed region the weight gradients run on a second stream next to the data
+        # gradients (conv.WGRAD_SIDE_STREAM_MAX_PIXELS) and two kernels that share the chip each take longer than alone;
+        # the roofline objects price a kernel against the whole chip, so this pass keeps everything on one stream
+        # (`exclusive_ms_per_step` in the JSON is what that costs; `value` comes from the timed region above)
+        side_pixels = ficonv.WGRAD_SIDE_STREAM_MAX_PIXELS
+        ficonv.WGRAD_SIDE_STREAM_MAX_PIXELS = 0
+        from feature_intertwiner_amd import model as fimodel
+        dead_side = fimodel._DEAD_SIDE
+        fimodel._DEAD_SIDE = False            # the mask head's unread batch back on the main stream, for the same reason
+        from feature_intertwiner_amd import sub_module as fisub, workflow as fiwork
+        keep_side = (fimodel._PROPOSAL_SIDE, fisub._BIG_SIDE, fiwork.META_SIDE_STREAM)
+        fimodel._PROPOSAL_SIDE = fisub._BIG_SIDE = fiwork.META_SIDE_STREAM = False     # (round 4's side-stream work as well)
+        t1 = time.perf_counter()
+        for _ in range(prof_steps):
+            step()
+        torch.cuda.synchronize()
+        prof_elapsed = time.perf_counter() - t1
+        ficonv.WGRAD_SIDE_STREAM_MAX_PIXELS = side_pixels
+        fimodel._DEAD_SIDE = dead_side
+        fimodel._PROPOSAL_SIDE, fisub._BIG_SIDE, fiwork.META_SIDE_STREAM = keep_side
+        _lib.prof_enable(False)
+        log = car.LAUNCH_LOG
+        car.LAUNCH_LOG = None
+        flop_log = ficonv.FLOP_LOG
+        ficonv.FLOP_LOG = None
+        shape_log = ficonv.SHAPE_LOG
+        ficonv.SHAPE_LOG = None
+        shape_log = shape_log[:len(shape_log) // prof_steps]       # the convolutions of ONE step
     # ---- the same step with the backward pass in its dense form, for reference (outside the timed region) ----------
     dense_ref = None
-    if world == 1 and not args.dense_backward and not args.no_dense_reference:
+    if args.full and world == 1 and not args.dense_backward and not args.no_dense_reference:
         keep = (ficonv.GATES, ficonv._UNSCALED_BACKWARD)
         ficonv.GATES = ficonv._UNSCALED_BACKWARD = False
         for _ in range(2):
@@ -928,7 +1021,7 @@ def _main():
                              "multi-reader gradients -- the same forward results and the same gradients as the default"}
     # ---- the default backward pass against its dense form on the SAME weights / inputs / draws (outside the timed region)
     backward_check = None
-    if world == 1 and sync is None and not args.dense_backward and not args.no_dense_reference:
+    if args.full and world == 1 and sync is None and not args.dense_backward and not args.no_dense_reference:
         # (not with the data-parallel engine attached: its autograd hooks expect begin() / sync() around a backward pass)
         from feature_intertwiner_amd.workflow import check_backward_forms
         lowp = args.conv_precision != "fp32"
@@ -951,18 +1044,19 @@ def _main():
         torch.cuda.synchronize()
     # ---- BASELINE configs[4], single-GPU slice, on the driver's record too (outside the timed region) -----------------
     cfg4_slice = None
-    if world == 1 and sync is None and args.config == "cfg3" and not args.no_dense_reference and not args.dense_backward and \
-            args.conv_precision == "fp32":
+    if args.full and world == 1 and sync is None and args.config == "cfg3" and not args.no_dense_reference and \
+            not args.dense_backward and args.conv_precision == "fp32":
         try:
             cfg4_slice = configs4_slice(dev)
         except Exception as ex:          # never takes the headline down
             cfg4_slice = {"error": repr(ex)}
     graph_ab = None
-    if world == 1 and sync is None and args.config == "cfg3" and not args.no_dense_reference and not args.dense_backward and \
-            args.conv_precision == "fp32" and args.batch_per_gpu != 2 and not args.no_issue_profile:
+    if args.full and world == 1 and sync is None and args.config == "cfg3" and not args.no_dense_reference and \
+            not args.dense_backward and args.conv_precision == "fp32" and args.batch_per_gpu != 2 and \
+            not args.no_issue_profile:
         graph_ab = graph_ab_child()
     per_rank_ms, rccl_ranks, overlap = None, None, None
-    if sync is not None and not share:
+    if args.full and sync is not None and not share:
         # a further pass with HIP events around every bucket's collective: how much of the exchange hides in backward
         sync.profile = []
         for _ in range(prof_steps):
@@ -971,7 +1065,7 @@ def _main():
         overlap = _overlap_report(sync.profile, prof_steps)
         sync.profile = None
     configs3 = None
-    if world > 1 and args.config == "cfg3" and args.batch_per_gpu != 2:
+    if args.full and world > 1 and args.config == "cfg3" and args.batch_per_gpu != 2:
         # BASELINE configs[3] quotes 2 images per GPU: the same model and engine on a 2-image shard, after the timed
         # region (2 warm-up + 6 timed steps, barrier + synchronize on both sides, MAX over ranks)
         batch2 = synthetic_batch(2, args.image_size, device=dev, seed=3000 + rank)
@@ -1033,6 +1127,7 @@ def _main():
         dist.all_gather(every, mine)
         per_rank_ms = [round(float(t.item()) / args.steps * 1e3, 3) for t in every]
         elapsed = max(float(t.item()) for t in every)                 # MAX over ranks
+    if args.full and world > 1:
         # which physical GPU every rank ran on (an all-gather of device UUIDs): N distinct devices = N RCCL ranks
         ids = [None] * world
         props = torch.cuda.get_device_properties(dev)
@@ -1045,164 +1140,167 @@ def _main():
         global_batch = args.batch_per_gpu * world
         ms_per_step = elapsed / args.steps * 1e3
         value = global_batch * args.steps / elapsed
-        # ---- roofline of the RoIAlign 7x7 forward kernel ---------------------------------
-        # (the Dev stage's maps are channels-last: crop_fwd_cl_kernel<7, 7>; NCHW kernel otherwise)
-        n7, ms7 = _lib.prof_get("crop_fwd_nhwc_7x7")
-        fwd7 = [e for e in log if e["crop"] == 7 and e["pyramid"] and e.get("nhwc")]
-        roi_kernel = "crop_fwd_nhwc_7x7"
-        if not (n7 and fwd7):
-            n7, ms7 = _lib.prof_get("crop_fwd_7x7")
-            fwd7 = [e for e in log if e["crop"] == 7 and e["pyramid"] and not e.get("nhwc")]
-            roi_kernel = "crop_fwd_7x7"
-        roof_roi = None
-        if n7 and fwd7:
-            e = fwd7[-1]
-            b_alg = crop_algorithmic_bytes(e)
-            b_dedup = crop_dedup_bytes(e, args.batch_per_gpu)
-            dur = ms7 / n7 * 1e-3
-            ach = b_alg / dur / 1e9
-            roof_roi = {"kernel": _lib.kernel_name(roi_kernel), "map_layout": "NHWC" if e.get("nhwc") else "NCHW",
-                    "bound": "hbm", "achieved": round(ach, 1),
-                    "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBPS, 4),
-                    "traffic": None, "algorithmic_bytes_per_launch": int(b_alg),
-                    "avg_launch_us": round(dur * 1e6, 2), "launches_timed": n7,
-                    "rois_per_launch": int(e["boxes"].size(0)), "bytes_model": "B_min (SURVEY 8d): output + each RoI's distinct taps",
-                    "dedup_bytes_per_launch": int(b_dedup),
-                    "achieved_dedup": round(b_dedup / dur / 1e9, 1), "frac_dedup": round(b_dedup / dur / 1e9 / HBM_PEAK_GBPS, 4),
-                    "dedup_model": "output + the UNION of all RoIs' taps per (image, level): the jittered-GT RoIs overlap, "
-                                   "so this is the most that can come from memory; the rest of B_min is served by L2"}
+        roof = roof_roi = conv_stack = nms_obj = sk_obj = None
         kern = {}
-        for k in _lib.KERNEL_IDS:
-            n, ms = _lib.prof_get(k)
-            if n:
-                kern[_lib.kernel_name(k)] = {"launches": n, "avg_us": round(ms / n * 1e3, 2),
-                                             "ms_per_step": round(ms / prof_steps, 3), "_key": k}
-        # ---- roofline of the DOMINANT kernel (largest share of the step) ------------------------
-        dom = max(kern.items(), key=lambda kv: kv[1]["ms_per_step"]) if kern else None
-        roof = None
-        if dom is not None and dom[1]["_key"] in flop_log:
-            launches, flops = flop_log[dom[1]["_key"]]
-            n, ms = _lib.prof_get(dom[1]["_key"])
-            ach = flops / (ms * 1e-3) / 1e12
-            peak = BF16_MFMA_PEAK_TFLOPS if "bf16" in dom[0] else FP32_MFMA_PEAK_TFLOPS
-            roof = {"kernel": dom[0], "bound": "mfma", "achieved": round(ach, 2), "peak": peak,
-                    "unit": "TFLOP/s", "frac": round(ach / peak, 4), "traffic": None,
-                    "algorithmic_flops_per_launch": int(flops / max(launches, 1)),
-                    "avg_launch_us": round(ms / n * 1e3, 2), "launches_timed": n,
-                    "share_of_step": round(dom[1]["ms_per_step"] / (prof_elapsed / prof_steps * 1e3), 4),
-                    "flops_model": "2*N*Cout*OH*OW*Cin*R*S per launch (%s)" % (
-                        "bf16 operands, fp32 accumulation" if "bf16" in dom[0] else "fp32, exact MFMA")}
-        elif roof_roi is not None:
-            roof = roof_roi
-        # ---- flop-weighted efficiency of the whole conv stack (every MFMA kernel instance) ----------
-        conv_stack = None
-        if flop_log:
-            tot_f = tot_ms = 0.0
-            per = {}
-            for name, v in kern.items():
-                if v["_key"] in flop_log:
-                    launches, flops = flop_log[v["_key"]]
-                    n, ms = _lib.prof_get(v["_key"])
-                    tot_f += flops
-                    tot_ms += ms
-                    per[name] = {"tflops": round(flops / (ms * 1e-3) / 1e12, 1), "ms_per_step": v["ms_per_step"],
-                                 "gflop_per_step": round(flops / prof_steps / 1e9, 1)}
-            if tot_ms > 0:
-                ach = tot_f / (tot_ms * 1e-3) / 1e12
-                cs_peak = FP32_MFMA_PEAK_TFLOPS if args.conv_precision == "fp32" else BF16_MFMA_PEAK_TFLOPS
-                conv_stack = {"achieved": round(ach, 2), "peak": cs_peak, "unit": "TFLOP/s",
-                              "frac": round(ach / cs_peak, 4),
-                              "tflop_per_step": round(tot_f / prof_steps / 1e12, 3),
-                              "ms_per_step": round(tot_ms / prof_steps, 2), "per_kernel": per,
-                              "note": "sum of algorithmic flops / sum of kernel time over every conv_fwd (forward + "
-                                      "data gradient) and conv_wgrad launch of the timed steps"}
-        # ---- NMS and Sinkhorn figures -------------------------------------------------------
-        n_m, ms_m = _lib.prof_get("nms_mask")
-        n_s, ms_s = _lib.prof_get("nms_scan")
-        nms_obj = None
-        if n_m:
-            nb, nbx = args.batch_per_gpu, cfg.RPN.PRE_NMS_LIMIT
-            b_nms = nb * (20 * nbx + 8 * nbx * ((nbx + 63) // 64))
-            us_m, us_s = ms_m / n_m * 1e3, (ms_s / n_s * 1e3 if n_s else 0.0)
-            nms_obj = {"images": nb, "boxes_per_image": nbx, "mask_kernel_us": round(us_m, 1), "scan_kernel_us": round(us_s, 1),
-                       "algorithmic_bytes": b_nms, "mask_GBps": round(b_nms / (us_m * 1e-6) / 1e9, 1),
-                       "mask_frac_hbm": round(b_nms / (us_m * 1e-6) / 1e9 / HBM_PEAK_GBPS, 4),
-                       "pair_tests_per_us": round(nb * nbx * nbx / 2 / us_m, 0),
-                       "bytes_model": "20*N read + 8*N*ceil(N/64) mask written, per image (SURVEY 8d); the kernel is "
-                                      "bound by the N^2/2 IoU tests (VALU), not by these bytes"}
-        n_k, ms_k = _lib.prof_get("sinkhorn")
-        sk_obj = None
-        if n_k:
-            ncls = cfg.DATASET.NUM_CLASSES - 1
-            fl = 3 * ncls * 2 * args.ot_L * 2 * 256 * 256
-            us_k = ms_k / n_k * 1e3
-            sk_obj = {"problems": 3 * ncls, "samples": 256, "L": args.ot_L, "kernel_us": round(us_k, 1),
-                      "GFLOPs": round(fl / (us_k * 1e-6) / 1e9, 1),
-                      "frac_fp32_vector_peak": round(fl / (us_k * 1e-6) / 1e12 / FP32_MFMA_PEAK_TFLOPS, 4),
-                      "bound": "on-chip (fp32 FMA + LDS/barrier latency); the HBM roofline does not apply: "
-                               "inputs are 2 x 256 floats per problem"}
-        # ---- HBM-side traffic of the dominant kernel and of RoIAlign from the PMC counters ----------------
-        if world == 1 and not args.no_pmc and roof is not None:
-            child = ["--backbone", args.backbone, "--image-size", str(args.image_size), "--batch-per-gpu",
-                     str(args.batch_per_gpu), "--rois", str(args.rois), "--ot-L", str(args.ot_L), "--conv-precision",
-                     args.conv_precision]
-            if args.mask_head_on_positive_slots:
-                child.append("--mask-head-on-positive-slots")
-            if args.dense_backward:
-                child.append("--dense-backward")
-            # kernel-name prefix the trace rows are matched on: "name<args" without the closing bracket for a template
-            # instantiation, the plain name otherwise (the 16-bit kernels' slots)
-            kn = roof["kernel"]
-            subs = [kn.split("<")[0] + "<" + kn.split("<")[1].rstrip(">") if "<" in kn else kn]
+        if args.full:
+            # ---- roofline of the RoIAlign 7x7 forward kernel ---------------------------------
+            # (the Dev stage's maps are channels-last: crop_fwd_cl_kernel<7, 7>; NCHW kernel otherwise)
+            n7, ms7 = _lib.prof_get("crop_fwd_nhwc_7x7")
+            fwd7 = [e for e in log if e["crop"] == 7 and e["pyramid"] and e.get("nhwc")]
+            roi_kernel = "crop_fwd_nhwc_7x7"
+            if not (n7 and fwd7):
+                n7, ms7 = _lib.prof_get("crop_fwd_7x7")
+                fwd7 = [e for e in log if e["crop"] == 7 and e["pyramid"] and not e.get("nhwc")]
+                roi_kernel = "crop_fwd_7x7"
+            roof_roi = None
+            if n7 and fwd7:
+                e = fwd7[-1]
+                b_alg = crop_algorithmic_bytes(e)
+                b_dedup = crop_dedup_bytes(e, args.batch_per_gpu)
+                dur = ms7 / n7 * 1e-3
+                ach = b_alg / dur / 1e9
+                roof_roi = {"kernel": _lib.kernel_name(roi_kernel), "map_layout": "NHWC" if e.get("nhwc") else "NCHW",
+                        "bound": "hbm", "achieved": round(ach, 1),
+                        "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBPS, 4),
+                        "traffic": None, "algorithmic_bytes_per_launch": int(b_alg),
+                        "avg_launch_us": round(dur * 1e6, 2), "launches_timed": n7,
+                        "rois_per_launch": int(e["boxes"].size(0)), "bytes_model": "B_min (SURVEY 8d): output + each RoI's distinct taps",
+                        "dedup_bytes_per_launch": int(b_dedup),
+                        "achieved_dedup": round(b_dedup / dur / 1e9, 1), "frac_dedup": round(b_dedup / dur / 1e9 / HBM_PEAK_GBPS, 4),
+                        "dedup_model": "output + the UNION of all RoIs' taps per (image, level): the jittered-GT RoIs overlap, "
+                                       "so this is the most that can come from memory; the rest of B_min is served by L2"}
+            kern = {}
+            for k in _lib.KERNEL_IDS:
+                n, ms = _lib.prof_get(k)
+                if n:
+                    kern[_lib.kernel_name(k)] = {"launches": n, "avg_us": round(ms / n * 1e3, 2),
+                                                 "ms_per_step": round(ms / prof_steps, 3), "_key": k}
+            # ---- roofline of the DOMINANT kernel (largest share of the step) ------------------------
+            dom = max(kern.items(), key=lambda kv: kv[1]["ms_per_step"]) if kern else None
+            roof = None
+            if dom is not None and dom[1]["_key"] in flop_log:
+                launches, flops = flop_log[dom[1]["_key"]]
+                n, ms = _lib.prof_get(dom[1]["_key"])
+                ach = flops / (ms * 1e-3) / 1e12
+                peak = BF16_MFMA_PEAK_TFLOPS if "bf16" in dom[0] else FP32_MFMA_PEAK_TFLOPS
+                roof = {"kernel": dom[0], "bound": "mfma", "achieved": round(ach, 2), "peak": peak,
+                        "unit": "TFLOP/s", "frac": round(ach / peak, 4), "traffic": None,
+                        "algorithmic_flops_per_launch": int(flops / max(launches, 1)),
+                        "avg_launch_us": round(ms / n * 1e3, 2), "launches_timed": n,
+                        "share_of_step": round(dom[1]["ms_per_step"] / (prof_elapsed / prof_steps * 1e3), 4),
+                        "flops_model": "2*N*Cout*OH*OW*Cin*R*S per launch (%s)" % (
+                            "bf16 operands, fp32 accumulation" if "bf16" in dom[0] else "fp32, exact MFMA")}
+            elif roof_roi is not None:
+                roof = roof_roi
+            # ---- flop-weighted efficiency of the whole conv stack (every MFMA kernel instance) ----------
+            conv_stack = None
+            if flop_log:
+                tot_f = tot_ms = 0.0
+                per = {}
+                for name, v in kern.items():
+                    if v["_key"] in flop_log:
+                        launches, flops = flop_log[v["_key"]]
+                        n, ms = _lib.prof_get(v["_key"])
+                        tot_f += flops
+                        tot_ms += ms
+                        per[name] = {"tflops": round(flops / (ms * 1e-3) / 1e12, 1), "ms_per_step": v["ms_per_step"],
+                                     "gflop_per_step": round(flops / prof_steps / 1e9, 1)}
+                if tot_ms > 0:
+                    ach = tot_f / (tot_ms * 1e-3) / 1e12
+                    cs_peak = FP32_MFMA_PEAK_TFLOPS if args.conv_precision == "fp32" else BF16_MFMA_PEAK_TFLOPS
+                    conv_stack = {"achieved": round(ach, 2), "peak": cs_peak, "unit": "TFLOP/s",
+                                  "frac": round(ach / cs_peak, 4),
+                                  "tflop_per_step": round(tot_f / prof_steps / 1e12, 3),
+                                  "ms_per_step": round(tot_ms / prof_steps, 2), "per_kernel": per,
+                                  "note": "sum of algorithmic flops / sum of kernel time over every conv_fwd (forward + "
+                                          "data gradient) and conv_wgrad launch of the timed steps"}
+            # ---- NMS and Sinkhorn figures -------------------------------------------------------
+            n_m, ms_m = _lib.prof_get("nms_mask")
+            n_s, ms_s = _lib.prof_get("nms_scan")
+            nms_obj = None
+            if n_m:
+                nb, nbx = args.batch_per_gpu, cfg.RPN.PRE_NMS_LIMIT
+                b_nms = nb * (20 * nbx + 8 * nbx * ((nbx + 63) // 64))
+                us_m, us_s = ms_m / n_m * 1e3, (ms_s / n_s * 1e3 if n_s else 0.0)
+                nms_obj = {"images": nb, "boxes_per_image": nbx, "mask_kernel_us": round(us_m, 1), "scan_kernel_us": round(us_s, 1),
+                           "algorithmic_bytes": b_nms, "mask_GBps": round(b_nms / (us_m * 1e-6) / 1e9, 1),
+                           "mask_frac_hbm": round(b_nms / (us_m * 1e-6) / 1e9 / HBM_PEAK_GBPS, 4),
+                           "pair_tests_per_us": round(nb * nbx * nbx / 2 / us_m, 0),
+                           "bytes_model": "20*N read + 8*N*ceil(N/64) mask written, per image (SURVEY 8d); the kernel is "
+                                          "bound by the N^2/2 IoU tests (VALU), not by these bytes"}
+            n_k, ms_k = _lib.prof_get("sinkhorn")
+            sk_obj = None
+            if n_k:
+                ncls = cfg.DATASET.NUM_CLASSES - 1
+                fl = 3 * ncls * 2 * args.ot_L * 2 * 256 * 256
+                us_k = ms_k / n_k * 1e3
+                sk_obj = {"problems": 3 * ncls, "samples": 256, "L": args.ot_L, "kernel_us": round(us_k, 1),
+                          "GFLOPs": round(fl / (us_k * 1e-6) / 1e9, 1),
+                          "frac_fp32_vector_peak": round(fl / (us_k * 1e-6) / 1e12 / FP32_MFMA_PEAK_TFLOPS, 4),
+                          "bound": "on-chip (fp32 FMA + LDS/barrier latency); the HBM roofline does not apply: "
+                                   "inputs are 2 x 256 floats per problem"}
+            # ---- HBM-side traffic of the dominant kernel and of RoIAlign from the PMC counters ----------------
+            if world == 1 and not args.no_pmc and roof is not None:
+                child = ["--backbone", args.backbone, "--image-size", str(args.image_size), "--batch-per-gpu",
+                         str(args.batch_per_gpu), "--rois", str(args.rois), "--ot-L", str(args.ot_L), "--conv-precision",
+                         args.conv_precision]
+                if args.mask_head_on_positive_slots:
+                    child.append("--mask-head-on-positive-slots")
+                if args.dense_backward:
+                    child.append("--dense-backward")
+                # kernel-name prefix the trace rows are matched on: "name<args" without the closing bracket for a template
+                # instantiation, the plain name otherwise (the 16-bit kernels' slots)
+                kn = roof["kernel"]
+                subs = [kn.split("<")[0] + "<" + kn.split("<")[1].rstrip(">") if "<" in kn else kn]
+                if roof_roi is not None:
+                    subs.append(roof_roi["kernel"].rstrip(">"))
+                t_p = time.time()
+                tr = pmc_traffic(subs, child)
+                if "error" in tr:
+                    roof["traffic_error"] = tr["error"]
+                else:
+                    for obj, sub in ((roof, subs[0]), (roof_roi, subs[1] if len(subs) > 1 else None)):
+                        if obj is not None and sub in tr:
+                            obj["traffic"] = int(tr[sub]["fetch"] + tr[sub]["write"])
+                            obj["traffic_detail"] = {"fetch_bytes": int(tr[sub]["fetch"]), "write_bytes": int(tr[sub]["write"]),
+                                                     "launches_counted": tr[sub]["launches"], "calibration": tr["calibration"],
+                                                     "method": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE in separate "
+                                                               "passes over the same train step, KB -> bytes, scaled by the factors "
+                                                               "measured on fi_calib_copy_kernel in the same run",
+                                                     "collection_s": round(time.time() - t_p, 1)}
+                    if roof_roi is not None and roof_roi.get("traffic"):
+                        roof_roi["traffic_GBps"] = round(roof_roi["traffic"] / (roof_roi["avg_launch_us"] * 1e-6) / 1e9, 1)
+                        roof_roi["traffic_frac_hbm"] = round(roof_roi["traffic_GBps"] / HBM_PEAK_GBPS, 4)
+            for v in kern.values():
+                v.pop("_key", None)
             if roof_roi is not None:
-                subs.append(roof_roi["kernel"].rstrip(">"))
-            t_p = time.time()
-            tr = pmc_traffic(subs, child)
-            if "error" in tr:
-                roof["traffic_error"] = tr["error"]
-            else:
-                for obj, sub in ((roof, subs[0]), (roof_roi, subs[1] if len(subs) > 1 else None)):
-                    if obj is not None and sub in tr:
-                        obj["traffic"] = int(tr[sub]["fetch"] + tr[sub]["write"])
-                        obj["traffic_detail"] = {"fetch_bytes": int(tr[sub]["fetch"]), "write_bytes": int(tr[sub]["write"]),
-                                                 "launches_counted": tr[sub]["launches"], "calibration": tr["calibration"],
-                                                 "method": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE in separate "
-                                                           "passes over the same train step, KB -> bytes, scaled by the factors "
-                                                           "measured on fi_calib_copy_kernel in the same run",
-                                                 "collection_s": round(time.time() - t_p, 1)}
-                if roof_roi is not None and roof_roi.get("traffic"):
-                    roof_roi["traffic_GBps"] = round(roof_roi["traffic"] / (roof_roi["avg_launch_us"] * 1e-6) / 1e9, 1)
-                    roof_roi["traffic_frac_hbm"] = round(roof_roi["traffic_GBps"] / HBM_PEAK_GBPS, 4)
-        for v in kern.values():
-            v.pop("_key", None)
-        if roof_roi is not None:
-            # lead with the memory-side figure (PMC traffic / duration) when there is one; B_min and the de-duplicated
-            # bytes stay next to it.  Then the north star's own shape (every per-kernel sum of the step has been read).
-            if roof_roi.get("traffic_frac_hbm") is not None:
-                roof_roi = dict([("frac_hbm_memory_side", roof_roi["traffic_frac_hbm"]),
-                                 ("frac_by_B_min", roof_roi["frac"])] + list(roof_roi.items()))
-            if world == 1:
-                try:
-                    ns = roof_roi["north_star_shape"] = north_star_roialign(dev)
-                    if not args.no_pmc:
-                        # the memory side of the north star's own launches: FETCH_SIZE / WRITE_SIZE of the two kernels in a
-                        # child that runs only them (calibrated on the copy kernel in the same process, as above)
-                        names = {"channels_last": "crop_fwd_cl_kernel<7, 7", "nchw": "crop_fwd_flat_kernel<7, 7"}
-                        tr2 = pmc_traffic(list(names.values()), [], timeout_s=120, child_flag="--pmc-child-roi")
-                        for lay, sub in names.items():
-                            if lay in ns and sub in tr2:
-                                t_b = tr2[sub]["fetch"] + tr2[sub]["write"]
-                                gbps = t_b / (ns[lay]["avg_launch_us"] * 1e-6) / 1e9
-                                ns[lay].update(traffic=int(t_b), fetch_bytes=int(tr2[sub]["fetch"]), write_bytes=int(tr2[sub]["write"]),
-                                               launches_counted=tr2[sub]["launches"], traffic_GBps=round(gbps, 1),
-                                               frac_hbm_memory_side=round(gbps / HBM_PEAK_GBPS, 4),
-                                               frac_by_B_min=ns[lay]["frac"])
-                        if "error" in tr2:
-                            ns["traffic_error"] = tr2["error"]
-                        elif "calibration" in tr2:
-                            ns["calibration"] = tr2["calibration"]
-                except Exception as ex:
-                    roof_roi["north_star_shape"] = {"error": repr(ex)}
+                # lead with the memory-side figure (PMC traffic / duration) when there is one; B_min and the de-duplicated
+                # bytes stay next to it.  Then the north star's own shape (every per-kernel sum of the step has been read).
+                if roof_roi.get("traffic_frac_hbm") is not None:
+                    roof_roi = dict([("frac_hbm_memory_side", roof_roi["traffic_frac_hbm"]),
+                                     ("frac_by_B_min", roof_roi["frac"])] + list(roof_roi.items()))
+                if world == 1:
+                    try:
+                        ns = roof_roi["north_star_shape"] = north_star_roialign(dev)
+                        if not args.no_pmc:
+                            # the memory side of the north star's own launches: FETCH_SIZE / WRITE_SIZE of the two kernels in a
+                            # child that runs only them (calibrated on the copy kernel in the same process, as above)
+                            names = {"channels_last": "crop_fwd_cl_kernel<7, 7", "nchw": "crop_fwd_flat_kernel<7, 7"}
+                            tr2 = pmc_traffic(list(names.values()), [], timeout_s=120, child_flag="--pmc-child-roi")
+                            for lay, sub in names.items():
+                                if lay in ns and sub in tr2:
+                                    t_b = tr2[sub]["fetch"] + tr2[sub]["write"]
+                                    gbps = t_b / (ns[lay]["avg_launch_us"] * 1e-6) / 1e9
+                                    ns[lay].update(traffic=int(t_b), fetch_bytes=int(tr2[sub]["fetch"]), write_bytes=int(tr2[sub]["write"]),
+                                                   launches_counted=tr2[sub]["launches"], traffic_GBps=round(gbps, 1),
+                                                   frac_hbm_memory_side=round(gbps / HBM_PEAK_GBPS, 4),
+                                                   frac_by_B_min=ns[lay]["frac"])
+                            if "error" in tr2:
+                                ns["traffic_error"] = tr2["error"]
+                            elif "calibration" in tr2:
+                                ns["calibration"] = tr2["calibration"]
+                    except Exception as ex:
+                        roof_roi["north_star_shape"] = {"error": repr(ex)}
         out = {
             "metric": "images/sec (train step, ResNet-101-FPN 1024^2, 512 RoIs)", "value": round(value, 4),
             "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1231,18 +1329,21 @@ def _main():
                                       "kernels (csrc/conv_bf16.hip; layers with Cin % 32 != 0 on the fp32 kernels)") +
                                      "; full-window convs and nn.Linear on the library GEMM"},
             "losses": {k: round(float(v), 5) for k, v in terms.items()},
-            "dense_backward_reference": dense_ref,
-            "backward_check": backward_check,
-            "configs4_slice": cfg4_slice,
-            "issue": issue, "two_images_per_gpu_graph_ab": graph_ab,
-            "roofline": roof, "roofline_roialign": roof_roi, "conv_stack": conv_stack, "nms": nms_obj, "sinkhorn": sk_obj,
-            "timing": {"timed_region": "%d steps, no event recording / logging" % args.steps,
-                       "profiled_pass": "%d further steps with HIP-event timing of every library kernel, weight gradients "
-                                        "and the mask head's unread batch on the main stream so that every duration is "
-                                        "the kernel alone on the chip (the timed region runs them on a second stream): "
-                                        "%.2f ms/step" % (prof_steps, prof_elapsed / prof_steps * 1e3)},
-            "kernels": kern,
+            "timing": {"timed_region": "%d steps, no event recording / logging" % args.steps},
         }
+        if args.full:
+            out.update({
+                "dense_backward_reference": dense_ref,
+                "backward_check": backward_check,
+                "configs4_slice": cfg4_slice,
+                "issue": issue, "two_images_per_gpu_graph_ab": graph_ab,
+                "roofline": roof, "roofline_roialign": roof_roi, "conv_stack": conv_stack, "nms": nms_obj, "sinkhorn": sk_obj,
+                "kernels": kern,
+            })
+            out["timing"]["profiled_pass"] = ("%d further steps with HIP-event timing of every library kernel, weight "
+                                              "gradients and the mask head's unread batch on the main stream so that every "
+                                              "duration is the kernel alone on the chip (the timed region runs them on a "
+                                              "second stream): %.2f ms/step" % (prof_steps, prof_elapsed / prof_steps * 1e3))
         if world > 1 or force_dp:
             out["data_parallel"] = {
                 "engine": "one process per GPU; gradients live in one arena per rank and every ~64 MB bucket is a "
@@ -1252,7 +1353,7 @@ def _main():
                 "ms_per_step_per_rank": per_rank_ms, "rccl_ranks": rccl_ranks, "overlap": overlap,
                 "streams": sync.stream_choice, "late_gradients": sync.late_gradients,
                 "configs3_shape": configs3}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 entries = [e for e in log if e["pyramid"] and e["crop"] in (7, 14) and e["boxes"].size(0) ==
                            args.batch_per_gpu * args.rois][-2:]

@@ -1,6 +1,6 @@
 #!/bin/bash
 # prints the headline numbers of one bench.py run (for scripts/ab_run.sh)
-python bench.py --no-cpu-baseline --no-pmc "$@" 2>/dev/null | python -c "
+python bench.py --full --no-cpu-baseline --no-pmc "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1])
 r = d['roofline']
