@@ -183,6 +183,9 @@ class _PyramidCrop(torch.autograd.Function):
                 _lib.ptr(g), ptrs, hs, ws, nl, _lib.ptr(boxes_c), _lib.ptr(ind_c), _lib.ptr(lvl_c),
                 boxes_c.shape[0], B, C, ctx.crop[0], ctx.crop[1], _lib.current_stream()),
                 "fi_pyramid_crop_backward")
+        if _lib.TAP is not None:
+            _lib.TAP("pyramid_crop_backward", grads=g, boxes=boxes_c, box_ind=ind_c, level=lvl_c, crop=ctx.crop[0],
+                     accumulate=accumulate, level_grads=grads)
         if accumulate:
             return (None,) * (7 + nl)
         out = list(grads)

@@ -1,6 +1,7 @@
 """HIP crop_and_resize (RoIAlign) vs the CPU oracle -- through the C ABI and through
 the reference-shaped Python operator.  Bar: bin assignment and forward values
 BIT-EXACT; backward (fp32 atomics, order not fixed) within a stated tolerance."""
+import collections
 import ctypes
 
 import numpy as np
@@ -195,21 +196,32 @@ def test_pyramid_matches_per_level_oracle(oracle):
             assert np.max(np.abs(g - e)) <= 2e-5 * (np.abs(e).max() + 1e-6)
 
 
-@pytest.mark.parametrize("C,crops", [(16, (7, 14)), (256, (7, 14)), (200, (7, 5)), (64, (1, 12)), (40, (14, 10))])
+# (cases past the first five: the box count and map sizes of the step's pyramid backward -- 1023 / 1100 boxes on either
+# side of the gather form's count rule for 7 x 7 crops, and 128-cell maps whose whole-image and straddling boxes span
+# more than the gather kernel's 64 cells and take its scatter fallback)
+_Wide = collections.namedtuple("_Wide", "crops boxes sizes")
+
+
+@pytest.mark.parametrize("C,crops", [(16, (7, 14)), (256, (7, 14)), (200, (7, 5)), (64, (1, 12)), (40, (14, 10)),
+                                     pytest.param(32, _Wide((7,), 1023, (64, 32, 16, 8)), id="32-boxes1023"),
+                                     pytest.param(32, _Wide((7,), 1100, (64, 32, 16, 8)), id="32-boxes1100"),
+                                     pytest.param(24, _Wide((7, 14), 1100, (128, 64, 32, 16)), id="24-maps128")])
 def test_pyramid_channels_last_matches_per_level_oracle(oracle, C, crops):
     """Maps in torch.channels_last memory format ([B,H,W,C]) take fi_pyramid_crop_*_nhwc: forward
-    BIT-EXACT vs the oracle (and hence vs the NCHW kernels), backward within the atomics tolerance -- and EQUAL to the
-    oracle in the deterministic tile-owner form (FI_CROP_BWD_CL_TILES=1: every cell's contributions are added in the
-    reference's serial order -- box, bin row, bin column, TL TR BL BR -- with the reference's fp32 products);
-    gradients returned in channels_last."""
+    BIT-EXACT vs the oracle (and hence vs the NCHW kernels), backward within the atomics tolerance and elementwise within
+    the fp32 bar of the float64 reference (tests/fp64_ref.py) -- and EQUAL to the oracle in the deterministic tile-owner
+    form (FI_CROP_BWD_CL_TILES=1: every cell's contributions are added in the reference's serial order -- box, bin row,
+    bin column, TL TR BL BR -- with the reference's fp32 products); gradients returned in channels_last."""
     import os
+    import fp64_ref
     from feature_intertwiner_amd.roi_align.crop_and_resize import LAUNCH_LOG, pyramid_crop_and_resize
     import feature_intertwiner_amd.roi_align.crop_and_resize as mod
+    N, sizes = (crops.boxes, crops.sizes) if isinstance(crops, _Wide) else (200, (64, 32, 16, 8))
+    crops = crops.crops if isinstance(crops, _Wide) else crops
     rs = np.random.RandomState(32 + C)
     B = 2
-    maps = [rs.standard_normal((B, C, s, s)).astype(np.float32) for s in (64, 32, 16, 8)]
-    N = 200
-    boxes = adversarial_boxes(rs, N, 64, 64)
+    maps = [rs.standard_normal((B, C, s, s)).astype(np.float32) for s in sizes]
+    boxes = adversarial_boxes(rs, N, sizes[0], sizes[0])
     ind = rs.randint(0, B, N).astype(np.int32)
     ind[5] = B + 3                                  # bad image index -> zero row
     level = rs.randint(1, 7, N).astype(np.int32)    # includes out-of-pyramid levels 1 and 6
@@ -249,6 +261,10 @@ def test_pyramid_channels_last_matches_per_level_oracle(oracle, C, crops):
                     assert np.array_equal(g, e), (crop, l, float(np.max(np.abs(g - e))))
                 else:
                     assert np.max(np.abs(g - e)) <= 2e-5 * (np.abs(e).max() + 1e-6)
+            worst = fp64_ref.check_crop_bwd([t.grad for t in tm], torch.from_numpy(G).to(DEV), boxes, ind, level, crop,
+                                            what="crop %d tiles=%s" % (crop, tiles))
+            print("C %d, %d boxes, maps %s, crop %d, tiles=%s: worst |d|/(2^-24 m) = %.2f" % (
+                C, N, sizes, crop, tiles, worst))
 
 
 def test_channels_last_full_size_equals_nchw_bitwise():

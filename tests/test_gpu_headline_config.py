@@ -11,6 +11,48 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
+def _tap_collector(taps):
+    """TAP callback: clones the tensors a launch read and wrote.  For the RoIAlign backward the level gradients are
+    cloned too (stream order makes the clone show exactly that launch's result) and their addresses kept, so that an
+    accumulating launch can be checked by its increment over the previous clone of the same buffers."""
+    def tap(name, **kw):
+        d = {}
+        for k, v in kw.items():
+            if torch.is_tensor(v):
+                d[k] = v.detach().clone()
+            elif isinstance(v, list):
+                d[k] = [m.detach().clone() for m in v] if name == "pyramid_crop_backward" else [m.detach() for m in v]
+            else:
+                d[k] = v
+        if name == "pyramid_crop_backward":
+            d["ptrs"] = tuple(m.data_ptr() for m in kw["level_grads"])
+        taps.append((name, d))
+    return tap
+
+
+def _check_crop_backward_taps(taps, label):
+    """Every RoIAlign backward launch of the step against the float64 reference (tests/fp64_ref.py), elementwise with the
+    fp32 bar; returns [(crop, boxes, accumulate, channels_last, worst |d| / (2^-24 m))]."""
+    import fp64_ref
+    prev, out = {}, []
+    for n, t in taps:
+        if n != "pyramid_crop_backward":
+            continue
+        before = prev.get(t["ptrs"]) if t["accumulate"] else None
+        assert before is not None or not t["accumulate"], "accumulating launch without an earlier launch on its buffers"
+        cl = t["level_grads"][0].dim() == 4 and not t["level_grads"][0].is_contiguous()
+        worst = fp64_ref.check_crop_bwd(t["level_grads"], t["grads"], t["boxes"], t["box_ind"], t["level"], t["crop"],
+                                        before=before, what="%s crop %d x %d boxes%s" % (
+                                            label, t["crop"], t["boxes"].shape[0], " (accumulate)" if before else ""))
+        prev[t["ptrs"]] = t["level_grads"]
+        out.append((t["crop"], int(t["boxes"].shape[0]), bool(t["accumulate"]), cl, worst))
+        t["level_grads"] = None
+    for r in out:
+        print("[%s] crop backward %2d x %2d, %5d boxes, accumulate=%d, channels_last=%d: worst |d|/(2^-24 m) = %.2f" % (
+            (label, r[0], r[0]) + r[1:]))
+    return out
+
+
 def test_configs2_full_size_two_steps_operators_vs_oracle(oracle):
     from feature_intertwiner_amd import _lib
     from feature_intertwiner_amd.config import make_config
@@ -27,9 +69,7 @@ def test_configs2_full_size_two_steps_operators_vs_oracle(oracle):
     first = float(train_step(model, opt, list(batch))["total"])       # step 1 (fills the history buffer)
 
     taps = []
-    _lib.TAP = lambda name, **kw: taps.append((name, {k: (v.detach().clone() if torch.is_tensor(v) else
-                                                         ([m.detach() for m in v] if isinstance(v, list) else v))
-                                                      for k, v in kw.items()}))
+    _lib.TAP = _tap_collector(taps)
     from feature_intertwiner_amd import conv as C
     C.FLOP_LOG = {}
     _lib.prof_reset()
@@ -108,7 +148,15 @@ def test_configs2_full_size_two_steps_operators_vs_oracle(oracle):
     assert x.shape == (240, 256, 1) and t["L"] == 50 and t["C_form"] == "cosine"
     exp = np.array([oracle.sinkhorn(x[p], y[p], t["eps_inv"], 50) for p in range(240)])
     assert np.all(np.abs(got - exp) <= 1e-4 * np.abs(exp) + 1e-7), np.abs(got - exp).max()
+
+    # ---- RoIAlign backward: every launch of the step, elementwise against float64 ----------------
+    # (the Dev stage's 14x14 (clearing) and 7x7 (accumulating, on the gather kernel by the box-count rule) channels-last
+    # launches over all 2048 RoIs; the big-box 14x14 crop builds no graph -- its class means are detached, Dev.forward --
+    # so it has no backward launch)
     del model, opt
+    torch.cuda.empty_cache()
+    bwd = _check_crop_backward_taps(taps, "configs[2]")
+    assert sorted((c, b, acc, cl) for c, b, acc, cl, _ in bwd) == [(7, 2048, True, True), (14, 2048, False, True)], bwd
     torch.cuda.empty_cache()
 
 
@@ -310,3 +358,63 @@ def test_whole_train_step_replays_as_one_hip_graph():
     assert float(terms["total"]) < float(first["total"])
     moved = sum(float((p.detach() - b).abs().max()) > 0 for p, b in zip(model.parameters(), before))
     assert moved > 100
+
+
+@pytest.mark.parametrize("name,kw,size,bs", [
+    ("configs[0]", dict(backbone="resnet50", image_size=512, batch_size=2, train_rois_per_image=64, dev_switch=False),
+     512, 2),
+    ("configs[1]", dict(backbone="resnet50", image_size=1024, batch_size=4, train_rois_per_image=256, ot_L=5), 1024, 4),
+], ids=["configs0", "configs1"])
+def test_baseline_configs_step_operators_vs_oracle(oracle, name, kw, size, bs):
+    """BASELINE configs[0] and configs[1] with the settings of test_gpu_detector.py::test_baseline_configs_run: in one
+    tapped train step, every forward RoIAlign BIT-EXACT against the oracle, the NMS keep indices exact, and every
+    RoIAlign backward launch elementwise against float64 -- configs[0] (DEV.SWITCH off) crops the NCHW FPN maps, so this
+    is the NCHW pyramid backward at step size; configs[1] has 4 x 256 = 1024 boxes, exactly at the gather form's count
+    rule."""
+    from feature_intertwiner_amd import _lib
+    from feature_intertwiner_amd.config import make_config
+    from feature_intertwiner_amd.model import MaskRCNN
+    from feature_intertwiner_amd.synthetic import SyntheticProposals, synthetic_batch
+    from feature_intertwiner_amd.workflow import set_optimizer, train_step
+    torch.manual_seed(2000)
+    cfg = make_config(**kw)
+    model = MaskRCNN(cfg).to(DEV)
+    opt = set_optimizer(model, cfg.TRAIN)
+    batch = synthetic_batch(bs, size, device=DEV)
+    model.external_proposals = SyntheticProposals(batch[2], size)
+    model.generator = torch.Generator(device=DEV).manual_seed(3)
+    train_step(model, opt, list(batch), do_meta=cfg.DEV.SWITCH)
+    taps = []
+    _lib.TAP = _tap_collector(taps)
+    try:
+        terms = train_step(model, opt, list(batch), do_meta=cfg.DEV.SWITCH)
+    finally:
+        _lib.TAP = None
+    torch.cuda.synchronize()
+    assert all(torch.isfinite(v) for v in terms.values()), terms
+    del model, opt
+    torch.cuda.empty_cache()
+    crops = [t for n, t in taps if n == "pyramid_crop"]
+    assert crops
+    for c in crops:
+        maps = [m.cpu().numpy() for m in c["maps"]]
+        boxes, ind, level = c["boxes"].cpu().numpy(), c["box_ind"].cpu().numpy(), c["level"].cpu().numpy()
+        got = c["crops"].cpu().numpy()
+        for l in range(2, 6):
+            sel = np.nonzero(level == l)[0]
+            if len(sel):
+                exp = oracle.crop_and_resize_forward(maps[l - 2], boxes[sel], ind[sel], c["crop"], c["crop"])
+                assert np.array_equal(got[sel].view(np.uint32), exp.view(np.uint32)), (name, c["crop"], l)
+        c["maps"] = None
+    nms = [t for n, t in taps if n == "nms_sorted" and not t["strict"]]
+    assert nms
+    for t in nms:
+        dets, keep, num = t["boxes"].cpu().numpy(), t["keep"].cpu().numpy(), t["num_out"].cpu().numpy()
+        for b in range(dets.shape[0]):
+            exp = oracle.pth_nms(dets[b], t["thresh"])[:t["max_keep"]]
+            assert int(num[b]) == len(exp) and np.array_equal(keep[b, :len(exp)], exp), (name, b)
+    bwd = _check_crop_backward_taps(taps, name)
+    assert len(bwd) >= 1, [n for n, _ in taps]
+    if name == "configs[0]":
+        assert any(not cl for _, _, _, cl, _ in bwd), bwd          # the NCHW pyramid backward ran inside the step
+    torch.cuda.empty_cache()
