@@ -286,8 +286,9 @@ __global__ __launch_bounds__(256) void rows_combine_kernel(const float *__restri
 // Phase 1, one workgroup per (row n, block of 64 channels): a wavefront owns a channel at a time, lanes run over pixels
 // (the plane's HW floats are contiguous); the per-row sums go to a workspace v[n][c], t[n].  Rows whose d is all zero
 // (RoIs that are not positives: three quarters of them) write zeros without reading x.  Phase 2, one workgroup per
-// (class, 64 channels): the rows of the class are summed in row order -- no atomics (thousands of rows share one
-// class: atomics on dW[k][c] serialise), deterministic.
+// (block of 64 channels, chunk of 256 rows): class_row_reduce_kernel adds the live rows into a per-class LDS table with
+// LDS atomics and flushes it with one global fp32 atomic per (class, channel) and workgroup -- the order of those
+// additions is not fixed, so dW / db are not bit-reproducible run to run.
 __global__ __launch_bounds__(256) void class_row_conv1x1_bwd_kernel(const float *__restrict__ d, const float *__restrict__ x,
                                                                     const float *__restrict__ w, const long *__restrict__ cls,
                                                                     float *__restrict__ dx, float *__restrict__ v,

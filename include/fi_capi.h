@@ -379,7 +379,13 @@ int fi_bn_fold_grad_batch(float *const *dw, const float *const *w, const float *
  * dbias (optional, [C]) additionally receives dshift[c] * scale[c] -- the gradient of a convolution bias
  * that was folded into the shift.  flags: FI_OUTPUTS_ZEROED = the caller has already zero-filled the
  * accumulated outputs (dshift, dgamma, dbias; dweight, dbias of fi_conv2d_weight_grad), e.g. as slices of
- * one arena cleared once per step, so the per-call fills are skipped. */
+ * one arena cleared once per step, so the per-call fills are skipped.
+ * dgamma recovers x_hat = (y - residual - beta) / gamma from the forward's rounded output: where gamma[c] == 0, y holds
+ * no x_hat and NOTHING is added to dgamma[c] (the true gradient sum g * x_hat is in general not zero), and elsewhere
+ * the error of dgamma[c] grows with (|y| + |residual| + |beta[c]|) / |gamma[c]| per term.  The fp32 step's default
+ * backward form (fi_bn_fold_grad: exact at gamma == 0) does not have this limit.  The callers (conv.py's fallback
+ * backward: 16-bit kernels, channels-last outputs, layers applied twice per step) do NOT check gamma: a BatchNorm with
+ * gamma[c] == 0 on those paths -- e.g. from a loaded checkpoint -- gets no gradient for gamma[c]. */
 #define FI_OUTPUTS_ZEROED 1
 int fi_bn_act_backward(const float *dy, const float *y, const float *scale, const float *gamma,
                        const float *beta, const float *residual, int N, int C, int HW, int relu,

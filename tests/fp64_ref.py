@@ -234,3 +234,153 @@ def check_crop_bwd(got_levels, grads, boxes, box_ind, level, crop, before=None, 
         else:
             worst = max(worst, check_bar(got, ref, mag, n, "%s level %d" % (what, li + 2)))
     return worst
+
+
+def check_increment(after, before, ref, mag, n, what=""):
+    """An ACCUMULATED output: (after - before) against the reference with the bar, widened by the rounding of the
+    accumulation, 2^-23 (|before| + |after|) (folded into m as in check_crop_bwd).  Returns the worst |d| / (2^-24 m)."""
+    a, b = _f64(after), _f64(before)
+    n_t = n if torch.is_tensor(n) else torch.full_like(a, float(n))
+    extra = 2.0 * (b.abs() + a.abs()) / (4.0 * torch.sqrt(_f64(n_t)) + 16.0)
+    return check_bar(a - b, ref, _f64(mag) + extra, n_t, what)
+
+
+# ---- BatchNorm / fully connected backward passes ----------------------------------------------------------------------
+def bn_act_bwd_ref(dy, y, xhat, gamma, beta, relu, residual=None):
+    """fi_bn_act_backward on [N,C,HW] tensors: y = act(gamma[c] * xhat + beta[c] (+ residual)) was the forward's fp32
+    output.  Returns g = dy * (y > 0 | 1) (fp64), dshift = sum g, dgamma = sum g * xhat (the TRUE xhat), each with its
+    m of the bar over N * HW terms.  The kernel recovers xhat as (y - residual - beta) / gamma from the rounded y, so
+    the m of dgamma carries the conditioning term (|y| + |residual| + |beta|) / |gamma| per element; a channel with
+    gamma == 0 gets m = inf (the header documents that the kernel writes 0 there)."""
+    dy, y, xh = _f64(dy), _f64(y), _f64(xhat)
+    g = dy * (y > 0).to(torch.float64) if relu else dy
+    ga = _f64(gamma).reshape(1, -1, 1)
+    be = _f64(beta).reshape(1, -1, 1)
+    r = _f64(residual).abs() if residual is not None else torch.zeros_like(y)
+    cond = (y.abs() + r + be.abs()) / ga.abs()            # inf where gamma == 0
+    dshift, m_shift = g.sum((0, 2)), g.abs().sum((0, 2))
+    dgamma = (g * xh).sum((0, 2))
+    m_gamma = (g.abs() * (xh.abs() + cond)).nan_to_num(nan=0.0, posinf=float("inf")).sum((0, 2))
+    return g, dshift, m_shift, dgamma, m_gamma
+
+
+def rows_mask_scale_ref(dy, y, relu):
+    """fi_rows_mask_scale on rows [M][N]: g = dy * (y > 0 | 1) (fp64) and colsum = sum over rows of g, with its m."""
+    dy = _f64(dy)
+    g = dy * (_f64(y) > 0).to(torch.float64) if relu else dy
+    return g, g.sum(0), g.abs().sum(0)
+
+
+def fold_grad_ref(dwp, w, s, scale, mean, var, eps, conv_bias=None):
+    """fi_bn_fold_grad in LOGICAL layouts: dwp (the weight gradient of the unscaled g) and w as [Cout][Cin][taps].
+    Returns dW = scale * dW', d gamma = inv_std (<W, dW'> + (conv_bias - mean) s), d bias = scale * s (fp64) and the m
+    of d gamma and d bias (the bar over K = Cin * taps)."""
+    dwp, w, s = _f64(dwp), _f64(w), _f64(s)
+    sc, inv = _f64(scale), 1.0 / torch.sqrt(_f64(var) + float(eps))
+    cb = _f64(conv_bias) if conv_bias is not None else torch.zeros_like(s)
+    Co = dwp.shape[0]
+    dot = (dwp.reshape(Co, -1) * w.reshape(Co, -1)).sum(1)
+    adot = (dwp.reshape(Co, -1) * w.reshape(Co, -1)).abs().sum(1)
+    mu = _f64(mean)
+    dgamma = inv * (dot + (cb - mu) * s)
+    m_gamma = inv * (adot + (cb - mu).abs() * s.abs())
+    return sc.reshape(-1, *([1] * (dwp.dim() - 1))) * dwp, dgamma, m_gamma, sc * s, (sc * s).abs()
+
+
+def class_row_bwd_ref(d, x, w, cls, num_classes, gated):
+    """fi_class_row_conv1x1_backward: d [N,HW], x [N,C,HW], w [K,C], cls [N].  Returns dx (fp64), dweight [K,C] and
+    dbias [K] with their m, and the number of terms per class (rows of the class * HW) for the bar."""
+    d, x, w = _f64(d), _f64(x), _f64(w)
+    cls = cls.long()
+    dx = w[cls][:, :, None] * d[:, None, :]
+    if gated:
+        dx = dx * (x > 0).to(torch.float64)
+    v, av = (x * d[:, None, :]).sum(2), (x * d[:, None, :]).abs().sum(2)
+    K, C = num_classes, x.shape[1]
+    dw = torch.zeros((K, C), dtype=torch.float64, device=x.device).index_add_(0, cls, v)
+    mw = torch.zeros_like(dw).index_add_(0, cls, av)
+    db = torch.zeros(K, dtype=torch.float64, device=x.device).index_add_(0, cls, d.sum(1))
+    mb = torch.zeros_like(db).index_add_(0, cls, d.abs().sum(1))
+    rows = torch.zeros(K, dtype=torch.float64, device=x.device).index_add_(0, cls, torch.ones_like(d[:, 0]))
+    return dx, dw, mw, db, mb, torch.clamp_min(rows * d.shape[1], 1.0)
+
+
+def _patch_index(shapes, image, anchor, per_loc, tap_shift=0):
+    """For every row and tap: (level, flat index into [B*C... per level]) -- as lists over the levels of (row, tap, h, w,
+    image) selections; tap_shift plants an off-by-one tap (for the tests of the bar)."""
+    image, anchor = image.long(), anchor.long()
+    starts, s = [], 0
+    for (B, C, H, W) in shapes:
+        starts.append(s)
+        s += H * W * per_loc
+    out = []
+    tap = torch.arange(9, device=image.device)
+    dh = (tap + tap_shift) // 3 - 1
+    dw = (tap + tap_shift) % 3 - 1
+    for l, (B, C, H, W) in enumerate(shapes):
+        end = starts[l + 1] if l + 1 < len(starts) else s
+        sel = (image >= 0) & (anchor >= starts[l]) & (anchor < end)
+        pix = (anchor - starts[l]) // per_loc
+        h = (pix // W)[:, None] + dh[None, :]
+        w = (pix % W)[:, None] + dw[None, :]
+        ok = sel[:, None] & (h >= 0) & (h < H) & (w >= 0) & (w < W)
+        out.append((ok, h.clamp(0, H - 1), w.clamp(0, W - 1)))
+    return out
+
+
+def patch_rows_ref(maps, image, anchor, per_loc, tap_shift=0):
+    """fi_pyramid_patch_rows_forward: out [rows][9][C] (fp64) = maps[l][image][c][h + tap/3 - 1][w + tap%3 - 1], 0
+    outside the map and for padding rows (image < 0)."""
+    shapes = [tuple(m.shape) for m in maps]
+    C = shapes[0][1]
+    out = torch.zeros((image.numel(), 9, C), dtype=torch.float64, device=maps[0].device)
+    img = image.long().clamp_min(0)[:, None].expand(-1, 9)
+    for m, (ok, h, w) in zip(maps, _patch_index(shapes, image, anchor, per_loc, tap_shift)):
+        vals = _f64(m).permute(0, 2, 3, 1)[img, h, w]            # [rows, 9, C]
+        out += vals * ok[..., None].to(torch.float64)
+    return out
+
+
+def patch_rows_bwd_ref(d, shapes, image, anchor, per_loc, tap_shift=0):
+    """fi_pyramid_patch_rows_backward: the gradients [B,C,H,W] of every level (fp64), their m and the number of
+    terms per element (at most 9 per row set)."""
+    d = _f64(d)
+    img = image.long().clamp_min(0)[:, None].expand(-1, 9)
+    gs, ms, ns = [], [], []
+    for (B, C, H, W), (ok, h, w) in zip(shapes, _patch_index(shapes, image, anchor, per_loc, tap_shift)):
+        flat = ((img * H + h) * W + w)[ok]
+        acc = torch.zeros((B * H * W, C), dtype=torch.float64, device=d.device).index_add_(0, flat, d[ok])
+        mag = torch.zeros_like(acc).index_add_(0, flat, d[ok].abs())
+        cnt = torch.zeros((B * H * W,), dtype=torch.float64, device=d.device).index_add_(
+            0, flat, torch.ones_like(flat, dtype=torch.float64))
+        gs.append(acc.reshape(B, H, W, C).permute(0, 3, 1, 2))
+        ms.append(mag.reshape(B, H, W, C).permute(0, 3, 1, 2))
+        ns.append(torch.clamp_min(cnt, 1.0).reshape(B, 1, H, W))
+    return gs, ms, ns
+
+
+# ---- clip + SGD ---------------------------------------------------------------------------------------------------------
+def grad_norm_ref(grads):
+    """sqrt(sum g^2) over all gradients in fp64, and the total element count (n of the bar)."""
+    tot = sum(float((_f64(g) ** 2).sum()) for g in grads)
+    return math.sqrt(tot), sum(g.numel() for g in grads)
+
+
+def clip_coef_ref(norm, max_norm):
+    """clip_grad_norm_'s factor min(1, max_norm / (norm + 1e-6))."""
+    return min(1.0, float(max_norm) / (float(norm) + 1e-6))
+
+
+def sgd_ref(p, g, buf, coef, wd, mom, lr):
+    """torch.optim.SGD's step (no dampening / nesterov) on a gradient scaled by coef, in fp64: returns (p', buf', g')
+    and their m -- the magnitudes the fp32 operations round against (each element goes through at most 5 of them)."""
+    p, g = _f64(p), _f64(g)
+    gs = g * float(coef)
+    u = gs + wd * p if wd else gs
+    mu = gs.abs() + (wd * p.abs() if wd else 0.0)
+    if buf is not None:
+        b = mom * _f64(buf) + u
+        mb = mom * _f64(buf).abs() + mu
+    else:
+        b, mb = u, mu
+    return p - lr * b, b, gs, p.abs() + lr * mb, mb, gs.abs()

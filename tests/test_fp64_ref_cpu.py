@@ -190,3 +190,165 @@ def test_bar_fails_a_crop_cell_missing_one_box(oracle):
     bad = got.copy()
     bad[k] -= one[k]
     assert R.bar_ratio(torch.from_numpy(bad), refs[0], mags[0], cnts[0])[1] > 1.0
+
+
+# ---- BatchNorm / class-row / patch-row / clip + SGD references (tests/test_gpu_step_glue_replay.py) ---------------------
+def _fails(fn):
+    with pytest.raises(AssertionError):
+        fn()
+
+
+@pytest.mark.parametrize("relu,res", [(True, False), (True, True), (False, False)])
+def test_bn_act_bwd_ref_equals_autograd_and_the_bar_takes_fp32(relu, res):
+    """dshift / dgamma of y = act(gamma xhat + beta (+ r)) against torch float64 autograd; an fp32 evaluation of the
+    kernel's formula (xhat recovered from the fp32 y) passes the bar even at |beta| / |gamma| = 2000, and dgamma summed
+    over a missing image fails it."""
+    g = torch.Generator().manual_seed(5)
+    N, C, HW = 3, 6, 23
+    xh = torch.randn(N, C, HW, generator=g, dtype=D)
+    ga = torch.randn(C, generator=g, dtype=D, requires_grad=True)
+    be = torch.randn(C, generator=g, dtype=D, requires_grad=True)
+    with torch.no_grad():
+        ga[1], be[1] = 1e-3, 2.0
+    r = torch.randn(N, C, HW, generator=g, dtype=D) if res else None
+    pre = ga.view(1, -1, 1) * xh + be.view(1, -1, 1) + (r if res else 0.0)
+    y = torch.relu(pre) if relu else pre
+    dy = torch.randn(N, C, HW, generator=g, dtype=D)
+    (y * dy).sum().backward()
+    gg, ds, ms, dgam, mg = R.bn_act_bwd_ref(dy, y.detach(), xh, ga.detach(), be.detach(), relu, r)
+    _close(ds, be.grad)
+    _close(dgam, ga.grad)
+    # the kernel's arithmetic in fp32, from the fp32 forward output
+    y32, r32 = y.detach().float(), (r.float() if res else 0.0)
+    g32 = torch.where(y32 > 0, dy.float(), torch.zeros_like(y32)) if relu else dy.float()
+    xr = (y32 - r32 - be.detach().float().view(1, -1, 1)) / ga.detach().float().view(1, -1, 1)
+    got = (g32 * xr).sum((0, 2))
+    R.check_bar(got, dgam, mg, N * HW, "fp32 dgamma")
+    R.check_bar(g32.sum((0, 2)), ds, ms, N * HW, "fp32 dshift")
+    _fails(lambda: R.check_bar((g32 * xr)[1:].sum((0, 2)), dgam, mg, N * HW))
+
+
+def test_rows_mask_scale_colsum_bar_rejects_a_dropped_row():
+    g = torch.Generator().manual_seed(6)
+    dy, y = torch.randn(300, 16, generator=g), torch.relu(torch.randn(300, 16, generator=g))
+    gr, cs, mc = R.rows_mask_scale_ref(dy, y, True)
+    _close(cs, torch.where(y > 0, dy, torch.zeros_like(dy)).double().sum(0))
+    R.check_bar(gr.float().sum(0), cs, mc, 300)
+    _fails(lambda: R.check_bar(gr.float()[torch.arange(300) != 137].sum(0), cs, mc, 300))
+
+
+@pytest.mark.parametrize("taps,bias", [(9, True), (1, False), (9, False)])
+def test_fold_grad_ref_equals_autograd_and_rejects_a_swapped_tap_order(taps, bias):
+    """d gamma / d conv-bias / dW of conv + eval-BatchNorm from the weight gradient of the unscaled g (fi_bn_fold_grad)
+    against torch float64 autograd of the whole layer; reading W in the other (tap-major) order fails the bar."""
+    g = torch.Generator().manual_seed(7 + taps)
+    k = 3 if taps == 9 else 1
+    N, Ci, Co, H = 2, 5, 4, 6
+    x = torch.randn(N, Ci, H, H, generator=g, dtype=D)
+    w = torch.randn(Co, Ci, k, k, generator=g, dtype=D, requires_grad=True)
+    cb = torch.randn(Co, generator=g, dtype=D, requires_grad=True) if bias else None
+    ga = torch.randn(Co, generator=g, dtype=D, requires_grad=True)
+    be = torch.randn(Co, generator=g, dtype=D)
+    mean, var, eps = torch.randn(Co, generator=g, dtype=D), torch.rand(Co, generator=g, dtype=D) + 0.1, 1e-3
+    z = F.conv2d(x, w, cb, padding=k // 2)
+    inv = 1.0 / torch.sqrt(var + eps)
+    y = (z - mean.view(1, -1, 1, 1)) * (ga * inv).view(1, -1, 1, 1) + be.view(1, -1, 1, 1)
+    gy = torch.randn(y.shape, generator=g, dtype=D)
+    (y * gy).sum().backward()
+    dwp = R.wgrad_ref(x, gy, k, k, pad=(k // 2, k // 2)).reshape(Co, Ci, taps)
+    s = gy.sum((0, 2, 3))
+    scale = ga.detach() * inv
+    dW, dgam, mg, dcb, mb = R.fold_grad_ref(dwp, w.detach().reshape(Co, Ci, taps), s, scale, mean, var, eps,
+                                            cb.detach() if bias else None)
+    _close(dW.reshape(w.shape), w.grad)
+    _close(dgam, ga.grad)
+    if bias:
+        _close(dcb, cb.grad)
+    got = R.fold_grad_ref(dwp.float(), w.detach().float().reshape(Co, Ci, taps), s.float(), scale.float(), mean.float(),
+                          var.float(), eps, cb.detach().float() if bias else None)[1]
+    R.check_bar(got.float(), dgam, mg, Ci * taps)
+    if taps > 1:
+        swapped = w.detach().permute(0, 2, 3, 1).reshape(Co, Ci, taps)        # W in tap-major order read as channel-major
+        bad = R.fold_grad_ref(dwp, swapped, s, scale, mean, var, eps, cb.detach() if bias else None)[1]
+        _fails(lambda: R.check_bar(bad, dgam, mg, Ci * taps))
+
+
+@pytest.mark.parametrize("gated", [False, True])
+def test_class_row_bwd_ref_equals_the_dense_autograd_and_rejects_a_double_accumulate(gated):
+    g = torch.Generator().manual_seed(8)
+    N, C, K, HW = 12, 5, 7, 10
+    x = torch.relu(torch.randn(N, C, HW, generator=g, dtype=D)).requires_grad_(True)
+    w = torch.randn(K, C, generator=g, dtype=D, requires_grad=True)
+    b = torch.randn(K, generator=g, dtype=D, requires_grad=True)
+    cls = torch.tensor([0, 3, 3, 6, 0, 0, 3, 1, 1, 6, 6, 3])
+    d = torch.randn(N, HW, generator=g, dtype=D)
+    d[1::2] = 0.0
+    y = torch.einsum("kc,nch->nkh", w, x) + b.view(1, -1, 1)
+    (y[torch.arange(N), cls] * d).sum().backward()
+    dx, dw, mw, db, mb, nk = R.class_row_bwd_ref(d, x.detach(), w.detach(), cls, K, gated)
+    _close(dw, w.grad)
+    _close(db, b.grad)
+    _close(dx, x.grad * (x.detach() > 0) if gated else x.grad)
+    before = torch.randn(K, C, generator=g, dtype=D)
+    R.check_increment((before + dw).float(), before.float(), dw, mw, nk[:, None].expand_as(dw))
+    _fails(lambda: R.check_increment((before + 2 * dw).float(), before.float(), dw, mw, nk[:, None].expand_as(dw)))
+
+
+def test_patch_rows_refs_are_adjoint_and_reject_an_off_by_one_tap():
+    """The backward reference is the adjoint of the forward one (torch autograd through the forward); border anchors,
+    level starts and padding rows included.  An off-by-one tap fails the bar (forward and backward)."""
+    g = torch.Generator().manual_seed(9)
+    shapes = [(2, 3, 5, 7), (2, 3, 3, 4)]
+    per = 3
+    total = sum(h * w * per for _, _, h, w in shapes)
+    anchor = torch.cat([torch.tensor([0, 5 * 7 * per, total - 1, per * 6, per * 28]),
+                        torch.randint(0, total, (20,), generator=g)])
+    image = torch.randint(0, 2, (25,), generator=g)
+    image[3] = -1
+    maps = [torch.randn(*s, generator=g, dtype=D, requires_grad=True) for s in shapes]
+    out = R.patch_rows_ref(maps, image, anchor, per)
+    # a hand-made element: row 0 is anchor 0 of level 0, pixel (0, 0); tap 4 is the centre, tap 0 reads outside
+    assert float(out[0, 4, 1]) == float(maps[0][image[0], 1, 0, 0]) and float(out[0, 0].abs().sum()) == 0.0
+    assert float(out[3].abs().sum()) == 0.0                                    # padding row
+    d = torch.randn(out.shape, generator=g, dtype=D)
+    (out * d).sum().backward()
+    gs, ms, ns = R.patch_rows_bwd_ref(d, shapes, image, anchor, per)
+    for gr, m in zip(gs, maps):
+        _close(gr, m.grad)
+    R.check_bar(gs[0].float(), gs[0], ms[0], ns[0])
+    bad_f = R.patch_rows_ref([m.detach() for m in maps], image, anchor, per, tap_shift=1)
+    _fails(lambda: R.check_bar(bad_f, out.detach(), out.detach().abs(), 9))
+    bad_b = R.patch_rows_bwd_ref(d, shapes, image, anchor, per, tap_shift=1)[0]
+    _fails(lambda: R.check_bar(bad_b[0], gs[0], ms[0], ns[0]))
+
+
+@pytest.mark.parametrize("momentum", [0.9, 0.0])
+def test_sgd_ref_equals_torch_clip_and_sgd_and_rejects_a_missing_clip(momentum):
+    g = torch.Generator().manual_seed(10)
+    ps = [torch.randn(s, generator=g, dtype=D) for s in ((6, 5), (7,), (3, 2, 2))]
+    gs = [torch.randn(p.shape, generator=g, dtype=D) * 3 for p in ps]
+    bufs = [torch.randn(p.shape, generator=g, dtype=D) for p in ps]
+    tp = [p.clone().requires_grad_(True) for p in ps]
+    for t, gr in zip(tp, gs):
+        t.grad = gr.clone()
+    opt = torch.optim.SGD([{"params": tp[:2], "weight_decay": 1e-4}, {"params": tp[2:], "weight_decay": 0.0}],
+                          lr=0.02, momentum=momentum)
+    if momentum:
+        for t, b in zip(tp, bufs):
+            opt.state[t]["momentum_buffer"] = b.clone()
+    norm = torch.nn.utils.clip_grad_norm_(tp, 5.0)
+    opt.step()
+    rn, n = R.grad_norm_ref(gs)
+    assert abs(rn - float(norm)) <= 1e-12 * rn and n == sum(p.numel() for p in ps)
+    coef = R.clip_coef_ref(rn, 5.0)
+    assert coef < 1.0
+    for i, (p, gr, b, t) in enumerate(zip(ps, gs, bufs, tp)):
+        wd = 1e-4 if i < 2 else 0.0
+        rp, rb, rg, mp, mb, mg = R.sgd_ref(p, gr, b if momentum else None, coef, wd, momentum, 0.02)
+        _close(rp, t.detach())
+        _close(rg, t.grad)
+        if momentum:
+            _close(rb, opt.state[t]["momentum_buffer"])
+        R.check_bar(rp.float(), rp, mp, 1)
+        bad = R.sgd_ref(p, gr, b if momentum else None, 1.0, wd, momentum, 0.02)[0]       # the clip factor left out
+        _fails(lambda: R.check_bar(bad, rp, mp, 1))

@@ -1,7 +1,7 @@
 """GPU: every convolution / GEMM launch of a real train step, replayed at the C ABI and checked ELEMENTWISE against a
 float64 reference (tests/fp64_ref.py) with the fp32 bar |got - ref| <= 2^-24 (4 sqrt(K) + 16) m.
 
-One train step runs with the library handle swapped for a recorder (as scripts/conv_shapes.py does); every fi_conv* /
+One train step runs with the library handle swapped for a recorder (tests/step_record.py); every fi_conv* /
 fi_gemm_nt* call is split by its argtypes (_lib.SIGNATURES) into integer arguments and pointer arguments, of which
 only NULL / non-NULL is kept, and deduplicated.  Each distinct record is then called again with the same integers on
 fresh seeded operands in the layouts the arguments declare (fragment-major 1x1 weights through
@@ -21,6 +21,7 @@ import pytest
 import torch
 
 import fp64_ref as R
+import step_record
 
 DEV = "cuda:0"
 
@@ -93,65 +94,12 @@ def test_replay_specs_match_the_library_signatures():
             assert is_int == (a not in _PTRS), (n, a, t)
 
 
-# ---- recording ----------------------------------------------------------------------------------------------------------
-def _is_null(v):
-    if v is None:
-        return True
-    if isinstance(v, ctypes.c_void_p):
-        return not v.value
-    return False
-
-
-class _Recorder(object):
-    """Stands in for the CDLL: the recorded entry points log (name, integer arguments, NULL pattern)."""
-
-    def __init__(self, real, records):
-        self._real = real
-        self._records = records
-
-    def __getattr__(self, name):
-        fn = getattr(self._real, name)
-        if not recorded_entry(name):
-            return fn
-        _, args = SPECS.get(name, (None, None))
-
-        def rec(*a):
-            if args is None:
-                self._records[(name, (), ())] = None
-            else:
-                ints = tuple((k, int(v)) for k, v in zip(args, a) if k not in _PTRS)
-                nulls = tuple((k, _is_null(v)) for k, v in zip(args, a) if k in _PTRS and k != "stream")
-                self._records[(name, ints, nulls)] = None
-            return fn(*a)
-        return rec
-
-
+# ---- recording (tests/step_record.py) ------------------------------------------------------------------------------------
 def _record_step(cfg_kw, size, batch_size, steps=2):
-    from feature_intertwiner_amd import _lib
-    from feature_intertwiner_amd.config import make_config
-    from feature_intertwiner_amd.model import MaskRCNN
-    from feature_intertwiner_amd.synthetic import SyntheticProposals, synthetic_batch
-    from feature_intertwiner_amd.workflow import set_optimizer, train_step
-    torch.manual_seed(2000)
-    cfg = make_config(**cfg_kw)
-    model = MaskRCNN(cfg).to(DEV)
-    opt = set_optimizer(model, cfg.TRAIN)
-    batch = synthetic_batch(batch_size, size, device=DEV, seed=2000)
-    model.external_proposals = SyntheticProposals(batch[2], size, seed=7)
-    model.generator = torch.Generator(device=DEV).manual_seed(11)
-    records = collections.OrderedDict()
-    real = _lib.load()
-    _lib._lib = _Recorder(real, records)
-    try:
-        for _ in range(steps):
-            terms = train_step(model, opt, list(batch))
-        torch.cuda.synchronize()
-    finally:
-        _lib._lib = real
-    assert all(torch.isfinite(v) for v in terms.values()), terms
-    del model, opt, batch
+    records, model = step_record.record_step(cfg_kw, size, batch_size, recorded_entry, SPECS, _PTRS, steps=steps)
+    del model
     torch.cuda.empty_cache()
-    return list(records)
+    return records
 
 
 # ---- replay -------------------------------------------------------------------------------------------------------------
