@@ -15,6 +15,10 @@ LIB_PATH = os.path.join(_HERE, "libfi_hip.so")
 SOURCES = ["fi_core.hip", "crop_and_resize.hip", "roi_pool.hip", "nms.hip", "sinkhorn.hip",
            "class_mean.hip", "conv_igemm.hip", "conv1x1_ring.hip", "conv_bf16.hip", "conv_f16.hip", "sgd.hip", "glue.hip", "proposal.hip", "targets.hip", "losses.hip", "dev_stage.hip", "meta_stats.hip"]
 HEADERS = ["fi_common.h", os.path.join("..", "..", "include", "fi_capi.h")]
+# the evaluation path (inference post-processing, include/fi_eval.h): its own library, linked against libfi_hip.so
+EVAL_LIB_PATH = os.path.join(_HERE, "libfi_eval.so")
+EVAL_SOURCES = ["unmold.hip"]
+EVAL_HEADERS = [os.path.join("..", "..", "include", "fi_eval.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
@@ -36,9 +40,9 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build_hip(force=False, verbose=False):
-    srcs = [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
-    hdrs = [os.path.normpath(os.path.join(CSRC, h)) for h in HEADERS]
+def _compile(sources, headers, force, verbose):
+    srcs = [os.path.join(CSRC, s) for s in sources if os.path.exists(os.path.join(CSRC, s))]
+    hdrs = [os.path.normpath(os.path.join(CSRC, h)) for h in headers]
     objs = []
     for s in srcs:
         o = s[:-4] + ".o"
@@ -49,8 +53,21 @@ def build_hip(force=False, verbose=False):
                 print(" ".join(cmd))
             subprocess.check_call(cmd)
         objs.append(o)
+    return objs
+
+
+def build_hip(force=False, verbose=False):
+    """Builds libfi_hip.so and libfi_eval.so; returns the path of the first."""
+    objs = _compile(SOURCES, HEADERS, force, verbose)
     if force or _stale(LIB_PATH, objs):
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    eval_objs = _compile(EVAL_SOURCES, HEADERS + EVAL_HEADERS, force, verbose)
+    if force or _stale(EVAL_LIB_PATH, eval_objs + [LIB_PATH]):
+        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", EVAL_LIB_PATH] + eval_objs + [
+            "-L" + _HERE, "-lfi_hip", "-Wl,-rpath,$ORIGIN"]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)

@@ -2,6 +2,7 @@
 reference): forward, meta (intertwiner) loss, loss composition, backward, gradient
 clipping, SGD step.  The reference's epoch/stage loops, logging, visdom and checkpointing
 are out of scope (SURVEY 2.1 #8)."""
+import numpy as np
 import torch
 
 import os
@@ -295,3 +296,32 @@ def check_backward_forms(model, inputs, bar=2e-5, attempts=3, **kw):
     r["attempts"] = len(events) + 1
     r["boundary_events"] = events
     return r
+
+
+def test_step(model, molded_images, image_metas, image_shapes=None, windows=None, coco_image_ids=None,
+              category_map=None, rle=True, dense=False):
+    """The loop body of test_model (lib/workflow.py:366-432, mode 'inference'): inference forward, unmolding of
+    every image's detections on the GPU (postprocess.unmold_detections) and, with a `category_map`, the COCO result
+    dicts.  `image_metas` is the reference's [bs, 8+K+1] meta array: the original shapes are taken from columns
+    1:4 and the windows from 4:8 (tools/image_utils.py:20-38), the COCO image ids from the last column unless
+    `coco_image_ids` is given.  `image_shapes` / `windows` override the meta columns.
+
+    Returns (results, unmolded): the result dicts (None without a category_map) and the per-image dicts of
+    unmold_detections."""
+    from .postprocess import coco_results, unmold_detections
+    detections, mrcnn_mask = model([molded_images, image_metas], mode='inference')
+    meta = image_metas.detach().cpu().numpy() if torch.is_tensor(image_metas) else np.asarray(image_metas)
+    if image_shapes is None:
+        image_shapes = meta[:, 1:3]
+    if windows is None:
+        windows = meta[:, 4:8] if meta.shape[1] > 4 else meta
+    unmolded = unmold_detections(detections, mrcnn_mask, image_shapes, np.asarray(windows, np.float32), rle=rle,
+                                 dense=dense)
+    if category_map is None:
+        return None, unmolded
+    if coco_image_ids is None:
+        coco_image_ids = [int(v) for v in meta[:, -1]]
+    return coco_results(unmolded, coco_image_ids, category_map), unmolded
+
+
+test_step.__test__ = False      # a product function, not a pytest test, when a test module imports it by name
