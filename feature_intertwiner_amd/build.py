@@ -19,6 +19,10 @@ HEADERS = ["fi_common.h", os.path.join("..", "..", "include", "fi_capi.h")]
 EVAL_LIB_PATH = os.path.join(_HERE, "libfi_eval.so")
 EVAL_SOURCES = ["unmold.hip"]
 EVAL_HEADERS = [os.path.join("..", "..", "include", "fi_eval.h")]
+# COCO evaluation of the result dicts (include/fi_cocoeval.h): a third library, built the same way
+COCOEVAL_LIB_PATH = os.path.join(_HERE, "libfi_cocoeval.so")
+COCOEVAL_SOURCES = ["cocoeval.hip"]
+COCOEVAL_HEADERS = [os.path.join("..", "..", "include", "fi_cocoeval.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
@@ -57,20 +61,22 @@ def _compile(sources, headers, force, verbose):
 
 
 def build_hip(force=False, verbose=False):
-    """Builds libfi_hip.so and libfi_eval.so; returns the path of the first."""
+    """Builds libfi_hip.so, libfi_eval.so and libfi_cocoeval.so; returns the path of the first."""
     objs = _compile(SOURCES, HEADERS, force, verbose)
     if force or _stale(LIB_PATH, objs):
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
-    eval_objs = _compile(EVAL_SOURCES, HEADERS + EVAL_HEADERS, force, verbose)
-    if force or _stale(EVAL_LIB_PATH, eval_objs + [LIB_PATH]):
-        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", EVAL_LIB_PATH] + eval_objs + [
-            "-L" + _HERE, "-lfi_hip", "-Wl,-rpath,$ORIGIN"]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
+    for lib, sources, headers in ((EVAL_LIB_PATH, EVAL_SOURCES, EVAL_HEADERS),
+                                  (COCOEVAL_LIB_PATH, COCOEVAL_SOURCES, COCOEVAL_HEADERS)):
+        objs = _compile(sources, HEADERS + headers, force, verbose)
+        if force or _stale(lib, objs + [LIB_PATH]):
+            cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + [
+                "-L" + _HERE, "-lfi_hip", "-Wl,-rpath,$ORIGIN"]
+            if verbose:
+                print(" ".join(cmd))
+            subprocess.check_call(cmd)
     return LIB_PATH
 
 
