@@ -106,6 +106,9 @@ SIGNATURES = {
     "fi_rows_mask_scale": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
     "fi_rows_affine_act": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
     "fi_conv2d_forward_live": (c_int, [c_void_p] * 7 + [c_int] * 16 + [c_void_p, c_void_p]),
+    "fi_conv2d_forward_plan": (c_int, [c_void_p] * 7 + [c_int] * 16 + [_ip]),
+    "fi_conv2d_weight_grad_plan": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 12 + [c_void_p, c_int, c_int, _ip]),
+    "fi_gemm_nt_plan": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p, _ip]),
     "fi_weight_transpose_batch": (c_int, [c_void_p, c_int, ctypes.c_long, c_void_p]),
     "fi_conv3x3_forward_bf16w": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p]),
     "fi_conv1x1_forward_bf16w": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
@@ -163,47 +166,19 @@ for _i, _bm in enumerate((64, 128)):
         KERNEL_IDS["conv_wgrad_bm%d_%s" % (_bm, _w)] = 22 + 4 * _i + _j
 
 
-def patch_mode(N, Cin, H, W, Cout, R, S, stride, padding, tap_major, out_hw_same, out_channels_last):
-    """Mirrors patch_eligible() in csrc/conv_igemm.hip: 0 = conv_fwd_kernel, 1 = conv3x3_patch_kernel<false>
-    (2-D tiles), 2 = conv3x3_patch_kernel<true> (flat tiles of 14-wide RoI maps)."""
-    if (R, S) != (3, 3) or tuple(stride) != (1, 1) or tuple(padding) != (1, 1):
-        return 0
-    if not tap_major or Cout <= 64 or not out_hw_same:
-        return 0
-    if out_channels_last and not (W % 16 == 0 and Cout % 128 == 0):
-        return 0
-    mt = (Cout + 127) // 128
-    if W % 16 == 0:
-        return 1 if ((N * H + 7) // 8) * (W // 16) * mt >= 256 else 0
-    if W < 16 and W % 2 == 0 and (W + 126) // W + 2 <= 13 and not out_channels_last:
-        return 2 if ((N * H * W + 127) // 128) * mt >= 512 else 0
-    return 0
-
-
-def reg1x1_mode(N, Cin, H, W, Cout, R, S, stride, padding, out_channels_last):
-    """Mirrors the conv1x1_reg_kernel dispatch in fi_conv2d_forward (csrc/conv_igemm.hip)."""
-    return ((R, S) == (1, 1) and tuple(stride) == (1, 1) and tuple(padding) == (0, 0) and not out_channels_last and
-            Cin % 32 == 0 and Cin >= 128 and Cout > 64 and (H * W) % 4 == 0 and
-            ((N * H * W + 127) // 128) * ((Cout + 127) // 128) >= 256)
-
-
-def conv_kernel_key(kind, cout, R, S, pixels=None, cin=None, batch=1):
-    """Name (KERNEL_IDS key) of the device kernel instance a convolution launch uses (mirrors
-    use_bm64() and the tile choice of fi_conv2d_weight_grad in csrc/conv_igemm.hip: 64-row tiles for
-    narrow layers and under-filled grids)."""
-    w = {(1, 1): "1x1", (3, 3): "3x3", (7, 7): "7x7"}.get((R, S), "other")
-    bm64 = cout <= 64
-    if kind == "fwd" and not bm64 and pixels is not None:
-        bm64 = ((pixels + 127) // 128) * ((cout + 127) // 128) < 512
-    if kind == "wgrad" and not bm64 and pixels is not None and cin is not None:
-        tiles128 = ((cin * R * S + 127) // 128) * ((cout + 127) // 128)
-        max_splits = (pixels + 511) // 512
-        bm64 = batch * tiles128 * min(max(1, 1024 // tiles128), max_splits) < 768      # batch: fi_conv2d_weight_grad_batch
-    return "conv_%s_bm%d_%s" % (kind, 64 if bm64 else 128, w)
+KERNEL_KEYS = {v: k for k, v in KERNEL_IDS.items()}      # id -> key: what the fi_*_plan queries answer with
 
 
 def kernel_name(key):
     return load().fi_prof_kernel_name(KERNEL_IDS[key]).decode()
+
+
+def planned_kernel(query, *args):
+    """KERNEL_IDS key of the kernel a launch with these arguments runs: `query` is the fi_*_plan entry of the launch entry
+    (a host-only function of the library, which decides), `args` its arguments up to the id it writes."""
+    k = ctypes.c_int(-1)
+    check(query(*args, ctypes.byref(k)), "kernel plan query")
+    return KERNEL_KEYS[k.value]
 
 _lib = None
 

@@ -23,7 +23,7 @@ import torch.nn.functional as F
 from . import _lib, grad_arena
 
 # bench.py sets this to a dict to accumulate the algorithmic flops (2*N*Cout*OH*OW*Cin*R*S) of
-# every launch, keyed by the device kernel instance (see _lib.conv_kernel_key).
+# every launch, keyed by the device kernel instance (the library's fi_*_plan queries name it, see _log_flops).
 FLOP_LOG = None
 LIVE_LOG = None
 # bench.py sets this to a list to record the (N, Cin, H, W, Cout, R, S, stride, padding) of every
@@ -63,13 +63,11 @@ def _log_shape(x, w, stride, padding):
                           tuple(stride), tuple(padding)))
 
 
-def _log_flops(kind, cout, R, S, flops, pixels=None, cin=None, patch=0, batch=1):
+def _log_flops(key, flops):
+    """key: the _lib.KERNEL_IDS name of the kernel the launch runs -- for the fp32 kernels _lib.planned_kernel()'s answer
+    to the launch's own arguments, asked only while FLOP_LOG is set."""
     if FLOP_LOG is not None:
-        if patch:
-            k = {1: "conv3x3_patch", 2: "conv3x3_patch_flat", 3: "conv1x1_reg"}[patch]
-        else:
-            k = ("conv_" + kind) if kind.startswith("bf16") else _lib.conv_kernel_key(kind, cout, R, S, pixels, cin, batch)
-        e = FLOP_LOG.setdefault(k, [0, 0])
+        e = FLOP_LOG.setdefault(key, [0, 0])
         e[0] += 1
         e[1] += flops
 
@@ -120,22 +118,15 @@ def _conv_fwd(x, w, b, stride, padding, relu=False, scale=None, residual=None, o
     if out_hw is not None:
         OH, OW = out_hw
     prec = _PRECISION if precision is None else precision
-    share = _live_share(live, N, "conv")    # (algorithmic flops: the live images only)
-    if not (prec in _LOWP and layout >= 1 and Cin % 32 == 0):
-        _log_flops("fwd", Cout, R, S, share * 2 * N * Cout * OH * OW * Cin * R * S, N * OH * OW,
-                   patch=(_lib.patch_mode(N, Cin, H, W, Cout, R, S, stride, padding, layout >= 1,
-                                          (OH, OW) == (H, W), out_channels_last) or
-                          (3 if _lib.reg1x1_mode(N, Cin, H, W, Cout, R, S, stride, padding, out_channels_last) else 0))
-                   if FLOP_LOG is not None else 0)
+    bf16 = prec in _LOWP and layout >= 1 and Cin % 32 == 0          # "bf16" here and below: either 16-bit operand type
+    flops = _live_share(live, N, "conv") * 2 * N * Cout * OH * OW * Cin * R * S     # (algorithmic: the live images only)
     y = torch.empty((N, Cout, OH, OW), device=x.device, dtype=torch.float32,
                     memory_format=torch.channels_last if out_channels_last else torch.contiguous_format)
-    bf16 = prec in _LOWP and layout >= 1 and Cin % 32 == 0          # "bf16" here and below: either 16-bit operand type
     if gate is not None:
         # y * (gate > 0) in the epilogue: the data gradient of a layer whose input is a ReLU output
         assert not out_channels_last and gate.shape == y.shape and gate.is_contiguous()
-    fn = _lowp_fn(L, "conv2d_forward_gated", prec) if bf16 else L.fi_conv2d_forward_gated
     if bf16:
-        _log_flops("bf16_fwd", Cout, R, S, share * 2 * N * Cout * OH * OW * Cin * R * S)
+        _log_flops("conv_bf16_fwd", flops)
         # 3x3 / stride 1 / pad 1 on maps whose width is a multiple of 16 (or 14-wide RoI maps): patch kernel with the
         # weights converted to bf16 once per step (cached like W^T) instead of inside every workgroup
         mt = (Cout + 127) // 128
@@ -172,28 +163,15 @@ def _conv_fwd(x, w, b, stride, padding, relu=False, scale=None, residual=None, o
                                            _lib.ptr(x), _lib.ptr(y), _lib.ptr(residual), _lib.ptr(gate)) == 1:
             w, layout = e[0], 3         # the persistent 1x1 kernel (csrc/conv1x1_ring.hip)
     with torch.cuda.device(x.device):
-        if live is not None and bf16:
-            _lib.check(_lowp_fn(L, "conv2d_forward_live", prec)(
-                _lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(scale), _lib.ptr(residual), _lib.ptr(gate), _lib.ptr(y), N, Cin,
-                H, W, Cout, R, S, stride[0], stride[1], padding[0], padding[1], 1 if relu else 0, layout,
+        # live [1] int32 on the device, or None: only the first live[0] images are real (fi_conv2d_forward_live)
+        args = (_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(scale), _lib.ptr(residual), _lib.ptr(gate), _lib.ptr(y),
+                N, Cin, H, W, Cout, R, S, stride[0], stride[1], padding[0], padding[1], 1 if relu else 0, layout,
                 OH if out_hw is not None else 0, OW if out_hw is not None else 0, 1 if out_channels_last else 0,
-                _lib.ptr(live), _lib.current_stream()), "fi_conv2d_forward_live_16")
-            return y
-        if live is not None and not bf16:
-            # live [1] int32 on the device: only the first live[0] images are real (fi_conv2d_forward_live)
-            _lib.check(L.fi_conv2d_forward_live(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(scale), _lib.ptr(residual),
-                                                _lib.ptr(gate), _lib.ptr(y), N, Cin, H, W, Cout, R, S, stride[0], stride[1],
-                                                padding[0], padding[1], 1 if relu else 0, layout,
-                                                OH if out_hw is not None else 0, OW if out_hw is not None else 0,
-                                                1 if out_channels_last else 0, _lib.ptr(live), _lib.current_stream()),
-                       "fi_conv2d_forward_live")
-            return y
-        _lib.check(fn(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(scale), _lib.ptr(residual), _lib.ptr(gate),
-                                       _lib.ptr(y), N, Cin, H, W, Cout,
-                                       R, S, stride[0], stride[1], padding[0], padding[1], 1 if relu else 0,
-                                       layout, OH if out_hw is not None else 0, OW if out_hw is not None else 0,
-                                       1 if out_channels_last else 0,
-                                       _lib.current_stream()), "fi_conv2d_forward")
+                _lib.ptr(live), _lib.current_stream())
+        if FLOP_LOG is not None and not bf16:
+            _log_flops(_lib.planned_kernel(L.fi_conv2d_forward_plan, *args[:-2]), flops)
+        fn = _lowp_fn(L, "conv2d_forward_live", prec) if bf16 else L.fi_conv2d_forward_live
+        _lib.check(fn(*args), "fi_conv2d_forward_live")
     return y
 
 
@@ -591,7 +569,8 @@ def _conv_backward(ctx_needs, x, w, dz, stride, padding, want_db=False, add_to_d
             dx = _relu_mask(dx, gate.contiguous(), dx)
     if ctx_needs[1]:
         # tap-major dW ([Cout,R,S,Cin]): 128 channels of one tap per column tile, or -- same-size stride-1
-        # layers with Cin == 64 (the C2 stage) -- 64 channels of two taps (mirrors wgrad_same_size())
+        # layers with Cin == 64 (the C2 stage) -- 64 channels of two taps.  `same` follows wgrad_same_size() and `hwc`
+        # wgrad_checked() in csrc/conv_igemm.hip, which rejects a tap-major request the geometry does not allow
         same = (stride == (1, 1) and dz.shape[2] == H and dz.shape[3] == W and (H * W) % 4 == 0 and W >= 4 and
                 x.numel() * 4 < 0x7fffff00 and dz.numel() * 4 < 0x7fffff00 and
                 x.data_ptr() % 16 == 0 and dz.data_ptr() % 16 == 0)
@@ -655,17 +634,18 @@ def _conv_backward(ctx_needs, x, w, dz, stride, padding, want_db=False, add_to_d
             if deferred:
                 pass
             elif bf16:
-                _log_flops("bf16_wgrad", Cout, R, S, 2 * N * Cout * dz.shape[2] * dz.shape[3] * Cin * R * S)
+                _log_flops("conv_bf16_wgrad", 2 * N * Cout * dz.shape[2] * dz.shape[3] * Cin * R * S)
                 _lib.check(_lowp_fn(L, "conv2d_weight_grad_db", precision)(_lib.ptr(x), _lib.ptr(dz), _lib.ptr(dw), _lib.ptr(db),
                                                         N, Cin, H, W, Cout,
                                                         R, S, stride[0], stride[1], padding[0], padding[1], flags,
                                                         _lib.current_stream()), "fi_conv2d_weight_grad_bf16")
             else:
-                _log_flops("wgrad", Cout, R, S, 2 * N * Cout * dz.shape[2] * dz.shape[3] * Cin * R * S,
-                           N * dz.shape[2] * dz.shape[3], Cin)
-                _lib.check(L.fi_conv2d_weight_grad(_lib.ptr(x), _lib.ptr(dz), _lib.ptr(dw), N, Cin, H, W, Cout,
-                                                   R, S, stride[0], stride[1], padding[0], padding[1], hwc,
-                                                   _lib.ptr(db), flags, _lib.current_stream()), "fi_conv2d_weight_grad")
+                args = (_lib.ptr(x), _lib.ptr(dz), _lib.ptr(dw), N, Cin, H, W, Cout, R, S, stride[0], stride[1], padding[0],
+                        padding[1], hwc, _lib.ptr(db), flags, _lib.current_stream())
+                if FLOP_LOG is not None:
+                    _log_flops(_lib.planned_kernel(L.fi_conv2d_weight_grad_plan, *args[:-1], 1),
+                               2 * N * Cout * dz.shape[2] * dz.shape[3] * Cin * R * S)
+                _lib.check(L.fi_conv2d_weight_grad(*args), "fi_conv2d_weight_grad")
             if after_wgrad is not None and not deferred:
                 after_wgrad(dw, db, bool(hwc and R * S > 1))        # (the 16-bit kernels write tap-major: hwc is set)
         if side is not None:
@@ -784,15 +764,16 @@ def _flush_wgrads(key):
         for t in xs + dzs:
             t.record_stream(side)
     with torch.cuda.device(xs[0].device), (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
+        geom = (N, Cin, H, W, Cout, R, S, 1, 1, padding[0], padding[1], 1)
         if lowp:
-            _log_flops("bf16_wgrad", Cout, R, S, 2.0 * n * N * H * W * Cout * Cin * R * S)
-        else:
-            _log_flops("wgrad", Cout, R, S, 2.0 * n * N * H * W * Cout * Cin * R * S, N * H * W, Cin, batch=n)
+            _log_flops("conv_bf16_wgrad", 2.0 * n * N * H * W * Cout * Cin * R * S)
+        elif FLOP_LOG is not None:         # (the batch entry takes pointer tables: the query gets the first problem and n)
+            _log_flops(_lib.planned_kernel(L.fi_conv2d_weight_grad_plan, _lib.ptr(xs[0]), _lib.ptr(dzs[0]), _lib.ptr(dws[0]),
+                                           *geom, _lib.ptr(items[0][3]) if has_db else None, _lib.OUTPUTS_ZEROED, n),
+                       2.0 * n * N * H * W * Cout * Cin * R * S)
         fn = _lowp_fn(L, "conv2d_weight_grad_batch", lowp) if lowp else L.fi_conv2d_weight_grad_batch
-        _lib.check(fn(arr(xs), arr(dzs), arr(dws),
-                                                 arr([it[3] for it in items]) if has_db else None, n, N, Cin, H, W, Cout,
-                                                 R, S, 1, 1, padding[0], padding[1], 1, _lib.OUTPUTS_ZEROED,
-                                                 _lib.current_stream()), "fi_conv2d_weight_grad_batch")
+        _lib.check(fn(arr(xs), arr(dzs), arr(dws), arr([it[3] for it in items]) if has_db else None, n, *geom,
+                      _lib.OUTPUTS_ZEROED, _lib.current_stream()), "fi_conv2d_weight_grad_batch")
         folds = [getattr(it[4], "fold", None) for it in items]
         if n > 1 and all(f is not None for f in folds) and len({(f[4], f[5] is None, f[6] is None, f[7] is None,
                                                                  f[0].is_contiguous()) for f in folds}) == 1:
@@ -1529,7 +1510,7 @@ def _gemm_nt(a, b, bias=None, relu=False, precision="fp32", live=None, scale=Non
     N = b.shape[0]
     if precision in _LOWP and M % 64 == 0 and K >= 64:
         y = torch.empty((M, N), device=a.device, dtype=torch.float32)
-        _log_flops("bf16_wgrad", M, 1, 1, _live_share(live, M) * 2.0 * M * N * K)
+        _log_flops("conv_bf16_wgrad", _live_share(live, M) * 2.0 * M * N * K)
         with torch.cuda.device(a.device):
             if live is not None:
                 _lib.check(_lowp_fn(L, "conv2d_weight_grad_rows", precision)(_lib.ptr(b), _lib.ptr(a), _lib.ptr(y), 1, N, 1, K,
@@ -1550,10 +1531,12 @@ def _gemm_nt(a, b, bias=None, relu=False, precision="fp32", live=None, scale=Non
         return torch.relu_(y) if relu else y
     y = torch.empty((M, N), device=a.device, dtype=torch.float32)
     ws = torch.empty((int(L.fi_gemm_nt_workspace_bytes(M, N, K)) + 3) // 4, device=a.device, dtype=torch.float32)
-    _log_flops("wgrad", M, 1, 1, _live_share(live, M) * 2.0 * M * N * K, K, N)
     with torch.cuda.device(a.device):
-        _lib.check(L.fi_gemm_nt_affine(_lib.ptr(a), _lib.ptr(b), _lib.ptr(scale), _lib.ptr(bias), _lib.ptr(y), M, N, K,
-                                       1 if relu else 0, _lib.ptr(ws), _lib.ptr(live), _lib.current_stream()), "fi_gemm_nt")
+        args = (_lib.ptr(a), _lib.ptr(b), _lib.ptr(scale), _lib.ptr(bias), _lib.ptr(y), M, N, K, 1 if relu else 0, _lib.ptr(ws),
+                _lib.ptr(live), _lib.current_stream())
+        if FLOP_LOG is not None:
+            _log_flops(_lib.planned_kernel(L.fi_gemm_nt_plan, *args[:-2]), _live_share(live, M) * 2.0 * M * N * K)
+        _lib.check(L.fi_gemm_nt_affine(*args), "fi_gemm_nt")
     return y
 
 

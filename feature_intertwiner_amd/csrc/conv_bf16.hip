@@ -1818,7 +1818,7 @@ int FI16(fi_conv2d_weight_grad, )(const float *x, const float *dy, float *dweigh
 
 static int wgrad16_impl(const float *x, const float *dy, float *dweight, float *dbias, int N, int Cin, int H,
                         int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
-                        int flags, fi_stream_t stream, const WgradBatch16 *batch);
+                        int flags, fi_stream_t stream, const WgradBatch16 *batch, const int32_t *rows_live_dev = nullptr);
 
 int FI16(fi_conv2d_weight_grad_db, )(const float *x, const float *dy, float *dweight, float *dbias, int N, int Cin, int H,
                                   int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
@@ -1830,16 +1830,12 @@ int FI16(fi_conv2d_weight_grad_db, )(const float *x, const float *dy, float *dwe
 
 // the weight gradient used as a GEMM (conv.linear on the 16-bit kernels: dweight [Cout = rows][Cin]) with a DEVICE count of
 // live rows: row tiles past it are skipped and stay at the zeros the call fills dweight with
-static const int32_t *g_rows_live = nullptr;      // (set around one launch by the entry point below; host-side only)
 int FI16(fi_conv2d_weight_grad_rows, )(const float *x, const float *dy, float *dweight, int N, int Cin, int H, int W,
                                     int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int flags,
                                     const int32_t *rows_live_dev, fi_stream_t stream)
 {
-    g_rows_live = rows_live_dev;
-    const int rc = wgrad16_impl(x, dy, dweight, nullptr, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w, flags,
-                                stream, nullptr);
-    g_rows_live = nullptr;
-    return rc;
+    return wgrad16_impl(x, dy, dweight, nullptr, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w, flags, stream,
+                        nullptr, rows_live_dev);
 }
 
 // n weight gradients of one geometry in one launch (see fi_conv2d_weight_grad_batch); loops when the geometry is not
@@ -1887,13 +1883,13 @@ int FI16(fi_conv2d_weight_grad_batch, )(const float *const *x, const float *cons
 
 static int wgrad16_impl(const float *x, const float *dy, float *dweight, float *dbias, int N, int Cin, int H,
                         int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
-                        int flags, fi_stream_t stream, const WgradBatch16 *batch)
+                        int flags, fi_stream_t stream, const WgradBatch16 *batch, const int32_t *rows_live_dev)
 {
     Geom g;
     int rc = make_geom(g, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w, 0, 0);
     if (rc != FI_OK) return rc;
     FI_REQUIRE(x && dy && dweight, "null pointer");
-    g.n_live = g_rows_live;              // only the flat kernel reads it
+    g.n_live = rows_live_dev;            // only the flat kernel reads it
     hipStream_t st = (hipStream_t)stream;
     const int RS = R * S;
     if (!(flags & FI_OUTPUTS_ZEROED)) {

@@ -1778,15 +1778,6 @@ __global__ __launch_bounds__(kThreads, 4) void conv_wgrad_vec_kernel(const float
     }
 }
 
-// 64-row tiles for narrow layers, and for grids that would leave the chip under-filled with
-// 128-row tiles (fewer than 2 workgroups per CU): C4/C5 of the backbone at batch 4.
-bool use_bm64(int Cout, int P)
-{
-    if (Cout <= 64) return true;
-    const long tiles128 = (long)fi::ceil_div(P, BN) * fi::ceil_div(Cout, 128);
-    return tiles128 < 512;
-}
-
 // conv3x3_patch_kernel: 3x3 / stride 1 / pad 1, same-size NCHW output, tap-major weights, 16-channel blocks,
 // 128-row Cout tiles, and at least 256 workgroups (one per CU: measured faster than the 64x64-tile kernel down
 // to there -- C4 of ResNet at batch 4 -- and slower below).
@@ -2030,6 +2021,129 @@ void launch_wgrad(const ConvGeom &g, const float *x, const float *dy, float *dw,
         hipLaunchKernelGGL((conv_wgrad_kernel<BM, 7, 7, false>), grid, dim3(kThreads), 0, st, x, dy, dw, g, p_per_split, dbias);
     else
         hipLaunchKernelGGL((conv_wgrad_kernel<BM, 0, 0, false>), grid, dim3(kThreads), 0, st, x, dy, dw, g, p_per_split, dbias);
+}
+
+// -------------------------------------------------------------------------------------
+// Kernel selection.  A planner validates the arguments and decides which kernel a call runs -- host arithmetic on
+// sizes, layouts and pointer VALUES, no HIP call -- and the entry point launches exactly what the plan says.  The
+// fi_*_plan queries at the end of this file run the same planners, so that whoever keeps books per kernel
+// (conv.FLOP_LOG, bench.py) asks the library instead of restating its rules.
+// -------------------------------------------------------------------------------------
+enum FwdPath { FWD_GENERIC, FWD_PATCH, FWD_PATCH_FLAT, FWD_REG1X1, FWD_RING };
+
+struct FwdPlan {
+    FwdPath path;
+    bool bm64;        // FWD_GENERIC: 64-row tiles (128 otherwise)
+    bool hwc;         // tap-major weights: the fast gather path
+    int kernel_id;    // FI_K_*: the profiling counter of the launch
+};
+
+// fi_conv2d_forward_live's arguments (without the live count and the stream) -> g (all but zero / n_live) and the plan
+int plan_forward(ConvGeom &g, FwdPlan &p, const float *x, const float *weight, const float *residual, const float *gate,
+                 const float *y, int N, int Cin, int H, int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h,
+                 int pad_w, int weight_layout, int out_h, int out_w, int output_layout)
+{
+    int rc = make_geom(g, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w, out_h, out_w);
+    if (rc != FI_OK) return rc;
+    FI_REQUIRE(x && weight && y, "null pointer");
+    FI_REQUIRE(output_layout == 0 || output_layout == 1, "output_layout: 0 = [N][Cout][OH][OW], 1 = [N][OH][OW][Cout]");
+    if (output_layout == 1) {
+        FI_REQUIRE(Cout % 4 == 0 && residual == nullptr && gate == nullptr && (uintptr_t)y % 16 == 0,
+                   "channels-last output needs Cout % 4 == 0, a 16-byte aligned y and no fused residual / gate");
+        FI_REQUIRE(Cin % BK == 0 && R * S <= 64 && (weight_layout >= 1 || R * S == 1),
+                   "channels-last output is implemented on the tap-major path (Cin % 16 == 0, weight_layout 1)");
+        g.out_nhwc = 1;
+    }
+    FI_REQUIRE(weight_layout >= 0 && weight_layout <= 3,
+               "weight_layout: 0 = [Cout][Cin][R][S], 1 = [Cout][R][S][Cin], 2 = 1 with the taps reversed, 3 = fragment-major 1x1");
+    // tap-major fast path: channels-last weights (any 1x1 weight is both layouts at once)
+    p.hwc = (Cin % BK == 0) && (R * S <= 64) && (weight_layout >= 1 || R * S == 1);
+    FI_REQUIRE(p.hwc || weight_layout == 0, "weight_layout 1/2/3 needs Cin % 16 == 0 and R*S <= 64");
+    g.flip = (weight_layout == 2) ? 1 : 0;
+    // generic kernel: 64-row tiles for narrow layers, and for grids that would leave the chip under-filled with
+    // 128-row tiles (fewer than 2 workgroups per CU): C4/C5 of the backbone at batch 4
+    p.bm64 = Cout <= 64 || (long)fi::ceil_div(g.P, BN) * fi::ceil_div(Cout, 128) < 512;
+    // fragment-major 1x1 weights (weight_layout 3, made by fi_weight_transpose_batch): the persistent ring form of the
+    // weights-in-registers kernel below (same counter)
+    if (weight_layout == 3) {
+        FI_REQUIRE(fi_conv1x1_ring_eligible(N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w, output_layout, x, y,
+                                            residual, gate) == 1,
+                   "weight_layout 3 (fragment-major 1x1 weights): shape or alignment not eligible for conv1x1_ring_kernel");
+        p.path = FWD_RING;
+        p.kernel_id = FI_K_CONV1X1_REG;
+        return FI_OK;
+    }
+    // 3x3 / stride 1 / pad 1 layers with enough tiles to fill the chip: input patch in LDS (conv3x3_patch_kernel)
+    int patch = getenv("FI_NO_PATCH") ? 0 : patch_eligible(g, p.hwc, weight_layout, x, y, residual);
+    if (patch == 2 && gate != nullptr && (uintptr_t)gate % 8 != 0) patch = 0;
+    // 1x1 / stride 1 layers: weights in registers, pixel tile staged 32 channels at a time (conv1x1_reg_kernel);
+    // layers with fewer than 128 input channels are bound by their output stream and measured faster on
+    // conv_fwd_kernel (4 workgroups per CU)
+    const bool reg1x1 = !getenv("FI_NO_REG1X1") && R == 1 && S == 1 && stride_h == 1 && stride_w == 1 && pad_h == 0 &&
+                        pad_w == 0 && !g.out_nhwc && Cin % P1_CB == 0 && Cin >= 128 && Cout > 64 && (H * W) % 4 == 0 &&
+                        (uintptr_t)x % 16 == 0 && (long)N * Cin * H * W < 2147483647L &&
+                        (long)fi::ceil_div(N * H * W, 128) * fi::ceil_div(Cout, 128) >= 256;
+    if (patch) {
+        p.path = patch == 2 ? FWD_PATCH_FLAT : FWD_PATCH;
+        p.kernel_id = FI_K_CONV3X3_PATCH + (patch - 1);
+    } else if (reg1x1) {
+        p.path = FWD_REG1X1;
+        p.kernel_id = FI_K_CONV1X1_REG;
+    } else {
+        p.path = FWD_GENERIC;
+        p.kernel_id = FI_K_CONV_FWD + (p.bm64 ? 0 : 4) + window_class(R, S);
+    }
+    return FI_OK;
+}
+
+struct WgradPlan {
+    int bm;           // tile rows (output channels): 64 or 128
+    int splits;       // pixel splits (grid.z)
+    int pps;          // pixels per split, a multiple of BK
+    int kernel_id;    // FI_K_*
+};
+
+// Tile and split choice of the weight-gradient kernels for dW [Cout][K] summed over P pixels, nb problems of that
+// geometry in one launch.  min_pix: fewest pixels a split may have; force_bm: 0 or a tile height to take whatever the
+// grid; target_wg: the workgroups tiles x splits should reach (the 1024 resident slots, 256 CUs x 4).
+WgradPlan plan_wgrad(int Cout, int K, int P, int R, int S, int nb, int min_pix, int force_bm, long target_wg)
+{
+    WgradPlan p;
+    // 64-row tiles for narrow layers, and when 128-row tiles x the admissible splits
+    // would fill less than 3/4 of the resident slots (C4/C5 1x1 layers at batch 4)
+    const long max_splits = ((long)P + min_pix - 1) / min_pix;
+    const long tiles128 = (long)fi::ceil_div(K, BN) * fi::ceil_div(Cout, 128);
+    const long per128 = 1024 / tiles128 < 1 ? 1 : 1024 / tiles128;
+    const long reach128 = nb * tiles128 * (per128 < max_splits ? per128 : max_splits);
+    p.bm = force_bm ? (Cout <= 64 ? 64 : force_bm) : ((Cout <= 64 || reach128 < 768) ? 64 : 128);
+    const long tiles = (long)fi::ceil_div(K, BN) * fi::ceil_div(Cout, p.bm);
+    // Split the pixel range so that tiles x splits fills the resident workgroup slots
+    // in ONE round: every workgroup has the same amount of work, so 1044 workgroups on 1024 slots take
+    // two rounds (the first version rounded UP and paid exactly that).
+    // (a batch of nb problems fills the slots together: fewer, longer pixel splits per problem -- the fixed cost of a
+    // workgroup, prologue and atomic epilogue, is paid per split)
+    const long want = target_wg / (tiles * nb);
+    int splits = (int)(want < 1 ? 1 : (want > max_splits ? max_splits : want));
+    if (splits < 1) splits = 1;
+    if (nb > 1) {
+        // a batch rarely fits ONE round exactly (12 layers x 36 tiles x 2 splits = 864 of 1024 slots): take the split
+        // count that minimises rounds x (pixels per split + the fixed cost of a workgroup, ~256 pixels' worth)
+        long best_cost = -1;
+        const long smax = max_splits < 64 ? max_splits : 64;
+        for (long sp = 1; sp <= smax; ++sp) {
+            const long total = tiles * nb * sp;
+            const long rounds = (total + 1023) / 1024;
+            const long cost = rounds * ((P + sp - 1) / sp + 256);
+            if (best_cost < 0 || cost < best_cost) {
+                best_cost = cost;
+                splits = (int)sp;
+            }
+        }
+    }
+    p.pps = fi::ceil_div(fi::ceil_div(P, splits), BK) * BK;
+    p.splits = fi::ceil_div(P, p.pps);
+    p.kernel_id = FI_K_CONV_WGRAD + (p.bm == 64 ? 0 : 4) + window_class(R, S);
+    return p;
 }
 
 // -------------------------------------------------------------------------------------
@@ -2319,23 +2433,10 @@ int fi_conv2d_forward_live(const float *x, const float *weight, const float *bia
                            fi_stream_t stream)
 {
     ConvGeom g;
-    int rc = make_geom(g, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w, out_h, out_w);
+    FwdPlan plan;
+    const int rc = plan_forward(g, plan, x, weight, residual, gate, y, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h,
+                                pad_w, weight_layout, out_h, out_w, output_layout);
     if (rc != FI_OK) return rc;
-    FI_REQUIRE(x && weight && y, "null pointer");
-    FI_REQUIRE(output_layout == 0 || output_layout == 1, "output_layout: 0 = [N][Cout][OH][OW], 1 = [N][OH][OW][Cout]");
-    if (output_layout == 1) {
-        FI_REQUIRE(Cout % 4 == 0 && residual == nullptr && gate == nullptr && (uintptr_t)y % 16 == 0,
-                   "channels-last output needs Cout % 4 == 0, a 16-byte aligned y and no fused residual / gate");
-        FI_REQUIRE(Cin % BK == 0 && R * S <= 64 && (weight_layout >= 1 || R * S == 1),
-                   "channels-last output is implemented on the tap-major path (Cin % 16 == 0, weight_layout 1)");
-        g.out_nhwc = 1;
-    }
-    FI_REQUIRE(weight_layout >= 0 && weight_layout <= 3,
-               "weight_layout: 0 = [Cout][Cin][R][S], 1 = [Cout][R][S][Cin], 2 = 1 with the taps reversed, 3 = fragment-major 1x1");
-    // tap-major fast path: channels-last weights (any 1x1 weight is both layouts at once)
-    const bool hwc = (Cin % BK == 0) && (R * S <= 64) && (weight_layout >= 1 || R * S == 1);
-    FI_REQUIRE(hwc || weight_layout == 0, "weight_layout 1/2/3 needs Cin % 16 == 0 and R*S <= 64");
-    g.flip = (weight_layout == 2) ? 1 : 0;
     g.zero = zero_page();
     FI_REQUIRE(g.zero != nullptr, "zero page lookup failed (no HIP device?)");
     g.n_live = n_live_dev;        // honoured by conv_fwd_kernel (every instantiation); the patch / 1x1 kernels compute all
@@ -2344,32 +2445,14 @@ int fi_conv2d_forward_live(const float *x, const float *weight, const float *bia
     if (getenv("FI_DBG_1X1")) relu |= (int)strtol(getenv("FI_DBG_1X1"), nullptr, 0);
 #endif
     const Epilogue ep = {bias, scale, residual, relu, gate};
-    const bool bm64 = use_bm64(Cout, g.P);
-    // 3x3 / stride 1 / pad 1 layers with enough tiles to fill the chip: input patch in LDS (conv3x3_patch_kernel)
-    int patch_mode = getenv("FI_NO_PATCH") ? 0 : patch_eligible(g, hwc, weight_layout, x, y, residual);
-    if (patch_mode == 2 && gate != nullptr && (uintptr_t)gate % 8 != 0) patch_mode = 0;
-    // 1x1 / stride 1 layers: weights in registers, pixel tile staged 32 channels at a time (conv1x1_reg_kernel);
-    // layers with fewer than 128 input channels are bound by their output stream and measured faster on
-    // conv_fwd_kernel (4 workgroups per CU)
-    const bool reg1x1 = !getenv("FI_NO_REG1X1") && R == 1 && S == 1 && stride_h == 1 && stride_w == 1 && pad_h == 0 &&
-                        pad_w == 0 && !g.out_nhwc && Cin % P1_CB == 0 && Cin >= 128 && Cout > 64 && (H * W) % 4 == 0 &&
-                        (uintptr_t)x % 16 == 0 && (long)N * Cin * H * W < 2147483647L &&
-                        (long)fi::ceil_div(N * H * W, 128) * fi::ceil_div(Cout, 128) >= 256;
-    // ... and with fragment-major weights (weight_layout 3, made by fi_weight_transpose_batch): the persistent ring form
-    if (weight_layout == 3) {
-        FI_REQUIRE(fi_conv1x1_ring_eligible(N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w, output_layout, x, y,
-                                            residual, gate) == 1,
-                   "weight_layout 3 (fragment-major 1x1 weights): shape or alignment not eligible for conv1x1_ring_kernel");
-        fi::ProfScope prof(FI_K_CONV1X1_REG, st);
+    fi::ProfScope prof(plan.kernel_id, st);
+    if (plan.path == FWD_RING) {
         const fi::RingArgs ra = {x, weight, bias, scale, residual, gate, y, g.zero, N, Cin, H * W, Cout, relu & 1};
         fi::launch_conv1x1_ring(ra, st);
         FI_HIP_CHECK(hipGetLastError());
         return FI_OK;
     }
-    fi::ProfScope prof(patch_mode ? FI_K_CONV3X3_PATCH + (patch_mode - 1)
-                       : reg1x1 ? FI_K_CONV1X1_REG
-                                : FI_K_CONV_FWD + (bm64 ? 0 : 4) + window_class(R, S), st);
-    if (reg1x1) {
+    if (plan.path == FWD_REG1X1) {
         Conv1x1Geom cg;
         cg.N = N; cg.Cin = Cin; cg.HW = H * W; cg.Cout = Cout;
         cg.ptiles = fi::ceil_div(N * H * W, 128);
@@ -2382,31 +2465,46 @@ int fi_conv2d_forward_live(const float *x, const float *weight, const float *bia
         FI_HIP_CHECK(hipGetLastError());
         return FI_OK;
     }
-    if (patch_mode) {
+    if (plan.path == FWD_PATCH || plan.path == FWD_PATCH_FLAT) {
+        const bool flat = plan.path == FWD_PATCH_FLAT;
         PatchGeom pg;
         pg.N = N; pg.Cin = Cin; pg.H = H; pg.W = W; pg.Cout = Cout;
         pg.flip = g.flip;
         pg.tiles_x = fi::ceil_div(W, PT_TW);
-        pg.ptiles = patch_mode == 2 ? fi::ceil_div(N * H * W, 128) : fi::ceil_div(N * H, PT_TH) * pg.tiles_x;
+        pg.ptiles = flat ? fi::ceil_div(N * H * W, 128) : fi::ceil_div(N * H, PT_TH) * pg.tiles_x;
         pg.mtiles = fi::ceil_div(Cout, 128);
         pg.vec4 = (W % 4 == 0 && (uintptr_t)y % 16 == 0 && (residual == nullptr || (uintptr_t)residual % 16 == 0) &&
                    (gate == nullptr || (uintptr_t)gate % 16 == 0)) ? 1 : 0;
         pg.out_nhwc = g.out_nhwc;
         pg.zero = g.zero;
         const long blocks = (long)fi::ceil_div(pg.ptiles, 8) * 8 * pg.mtiles;
-        if (patch_mode == 2)
+        if (flat)
             hipLaunchKernelGGL(conv3x3_patch_kernel<true>, dim3((unsigned)blocks), dim3(kThreads), 0, st, x, weight, ep, y, pg);
         else
             hipLaunchKernelGGL(conv3x3_patch_kernel<false>, dim3((unsigned)blocks), dim3(kThreads), 0, st, x, weight, ep, y, pg);
         FI_HIP_CHECK(hipGetLastError());
         return FI_OK;
     }
-    if (bm64)
-        launch_fwd<64>(g, x, weight, ep, y, hwc, st);
+    if (plan.bm64)
+        launch_fwd<64>(g, x, weight, ep, y, plan.hwc, st);
     else
-        launch_fwd<128>(g, x, weight, ep, y, hwc, st);
+        launch_fwd<128>(g, x, weight, ep, y, plan.hwc, st);
     FI_HIP_CHECK(hipGetLastError());
     return FI_OK;
+}
+
+int fi_conv2d_forward_plan(const float *x, const float *weight, const float *bias, const float *scale,
+                           const float *residual, const float *gate, float *y, int N, int Cin, int H, int W,
+                           int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int relu,
+                           int weight_layout, int out_h, int out_w, int output_layout, int *kernel_id)
+{
+    FI_REQUIRE(kernel_id != nullptr, "null pointer");
+    ConvGeom g;
+    FwdPlan plan;
+    const int rc = plan_forward(g, plan, x, weight, residual, gate, y, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h,
+                                pad_w, weight_layout, out_h, out_w, output_layout);
+    if (rc == FI_OK) *kernel_id = plan.kernel_id;
+    return rc;
 }
 
 int fi_bn_act_backward(const float *dy, const float *y, const float *scale, const float *gamma,
@@ -2465,6 +2563,40 @@ static bool wgrad_batchable(const ConvGeom &g, const float *x, const float *dy, 
     return hwc && wgrad_same_size(g, x, dy);
 }
 
+// fi_conv2d_weight_grad's argument checks -> g (all but zero) and hwc
+static int wgrad_checked(ConvGeom &g, bool &hwc, const float *x, const float *dy, const float *dweight, int N, int Cin, int H,
+                         int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int weight_layout)
+{
+    int rc = make_geom(g, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w);
+    if (rc != FI_OK) return rc;
+    FI_REQUIRE(x && dy && dweight, "null pointer");
+    FI_REQUIRE(weight_layout == 0 || weight_layout == 1, "weight_layout: 0 = [Cout][Cin][R][S], 1 = [Cout][R][S][Cin]");
+    // tap-major dW: 128 input channels of one tap per column tile, or (Cin == 64, row-major kernel only)
+    // the 64 channels of two taps
+    const bool half = (Cin == 64) && wgrad_same_size(g, x, dy);
+    hwc = ((Cin % BN == 0) || half) && (weight_layout == 1 || R * S == 1);
+    FI_REQUIRE(hwc || weight_layout == 0,
+               "weight_layout 1 needs Cin % 128 == 0, or Cin == 64 on a same-size stride-1 layer");
+    return FI_OK;
+}
+
+// the plan of a launch that carries nb problems of geometry g
+static WgradPlan wgrad_conv_plan(const ConvGeom &g, int nb)
+{
+    static const int min_pix = getenv("FI_WG_MINPIX") ? atoi(getenv("FI_WG_MINPIX")) : 512;      // tuning knobs (scripts/)
+    static const int force_bm = getenv("FI_WG_BM") ? atoi(getenv("FI_WG_BM")) : 0;
+    return plan_wgrad(g.Cout, g.K, g.P, g.R, g.S, nb, min_pix, force_bm, 1024);
+}
+
+// how many of n same-geometry problems fi_conv2d_weight_grad_batch puts into its first launch (1: it loops over them)
+static int wgrad_batch_size(bool batchable, int n, int flags, bool uniform_db)
+{
+    // one launch only for the row-major kernel, with the outputs pre-zeroed by the caller and uniform bias use;
+    // anything else: one launch per problem (same results)
+    if (!batchable || n == 1 || !(flags & FI_OUTPUTS_ZEROED) || !uniform_db) return 1;
+    return n < kWgBatchMax ? n : kWgBatchMax;
+}
+
 static int wgrad_impl(const float *x, const float *dy, float *dweight, int N, int Cin, int H,
                       int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h,
                       int pad_w, int weight_layout, float *dbias, int flags, fi_stream_t stream, const WgradBatch *batch);
@@ -2494,9 +2626,7 @@ int fi_conv2d_weight_grad_batch(const float *const *x, const float *const *dy, f
         any_db = any_db || has;
         all_db = all_db && has;
     }
-    // one launch only for the row-major kernel, with the outputs pre-zeroed by the caller and uniform bias use;
-    // anything else: one launch per problem (same results)
-    if (!ok || n == 1 || !(flags & FI_OUTPUTS_ZEROED) || (any_db && !all_db)) {
+    if (wgrad_batch_size(ok, n, flags, !any_db || all_db) == 1) {
         for (int i = 0; i < n; ++i) {
             rc = wgrad_impl(x[i], dy[i], dweight[i], N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w,
                             weight_layout, dbias ? dbias[i] : nullptr, flags, stream, nullptr);
@@ -2523,16 +2653,11 @@ static int wgrad_impl(const float *x, const float *dy, float *dweight, int N, in
                       int pad_w, int weight_layout, float *dbias, int flags, fi_stream_t stream, const WgradBatch *batch)
 {
     ConvGeom g;
-    int rc = make_geom(g, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w);
+    bool hwc;
+    const int rc = wgrad_checked(g, hwc, x, dy, dweight, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w,
+                                 weight_layout);
     if (rc != FI_OK) return rc;
-    FI_REQUIRE(x && dy && dweight, "null pointer");
-    FI_REQUIRE(weight_layout == 0 || weight_layout == 1, "weight_layout: 0 = [Cout][Cin][R][S], 1 = [Cout][R][S][Cin]");
-    // tap-major dW: 128 input channels of one tap per column tile, or (Cin == 64, row-major kernel only)
-    // the 64 channels of two taps
-    const bool half = (Cin == 64) && wgrad_same_size(g, x, dy);
-    const bool hwc = ((Cin % BN == 0) || half) && (weight_layout == 1 || R * S == 1);
-    FI_REQUIRE(hwc || weight_layout == 0,
-               "weight_layout 1 needs Cin % 128 == 0, or Cin == 64 on a same-size stride-1 layer");
+    const WgradPlan plan = wgrad_conv_plan(g, batch ? batch->n : 1);
     g.zero = zero_page();
     FI_REQUIRE(g.zero != nullptr, "zero page lookup failed (no HIP device?)");
     hipStream_t st = (hipStream_t)stream;
@@ -2540,49 +2665,27 @@ static int wgrad_impl(const float *x, const float *dy, float *dweight, int N, in
         FI_HIP_CHECK(hipMemsetAsync(dweight, 0, sizeof(float) * (size_t)Cout * g.K, st));
         if (dbias) FI_HIP_CHECK(hipMemsetAsync(dbias, 0, sizeof(float) * (size_t)Cout, st));
     }
-    // 64-row tiles for narrow layers, and when 128-row tiles x the admissible splits (>= 512 pixels each)
-    // would fill less than 3/4 of the resident slots (C4/C5 1x1 layers at batch 4)
-    static const int min_pix = getenv("FI_WG_MINPIX") ? atoi(getenv("FI_WG_MINPIX")) : 512;      // tuning knobs (scripts/)
-    static const int force_bm = getenv("FI_WG_BM") ? atoi(getenv("FI_WG_BM")) : 0;
-    const long max_splits0 = (g.P + min_pix - 1) / min_pix;
-    const long tiles128 = (long)fi::ceil_div(g.K, BN) * fi::ceil_div(Cout, 128);
-    const long reach128 = (batch ? batch->n : 1) * tiles128 * (1024 / tiles128 < max_splits0 ? (1024 / tiles128 < 1 ? 1 : 1024 / tiles128) : max_splits0);
-    const int BMsel = force_bm ? (Cout <= 64 ? 64 : force_bm) : ((Cout <= 64 || reach128 < 768) ? 64 : 128);
-    const long tiles = (long)fi::ceil_div(g.K, BN) * fi::ceil_div(Cout, BMsel);
-    // Split the pixel range so that tiles x splits fills the 1024 resident workgroup slots (256 CUs x 4)
-    // in ONE round: every workgroup has the same amount of work, so 1044 workgroups on 1024 slots take
-    // two rounds (the first version rounded UP and paid exactly that).  At least 512 pixels per split.
-    // (a batch of nb problems fills the slots together: fewer, longer pixel splits per problem -- the fixed cost of a
-    // workgroup, prologue and atomic epilogue, is paid per split)
-    const int nb = batch ? batch->n : 1;
-    long want = 1024 / (tiles * nb);
-    long max_splits = (g.P + min_pix - 1) / min_pix;
-    int splits = (int)(want < 1 ? 1 : (want > max_splits ? max_splits : want));
-    if (splits < 1) splits = 1;
-    if (nb > 1) {
-        // a batch rarely fits ONE round exactly (12 layers x 36 tiles x 2 splits = 864 of 1024 slots): take the split
-        // count that minimises rounds x (pixels per split + the fixed cost of a workgroup, ~256 pixels' worth)
-        long best_cost = -1;
-        const long smax = max_splits < 64 ? max_splits : 64;
-        for (long sp = 1; sp <= smax; ++sp) {
-            const long total = tiles * nb * sp;
-            const long rounds = (total + 1023) / 1024;
-            const long cost = rounds * ((g.P + sp - 1) / sp + 256);
-            if (best_cost < 0 || cost < best_cost) {
-                best_cost = cost;
-                splits = (int)sp;
-            }
-        }
-    }
-    int pps = fi::ceil_div(g.P, splits);
-    pps = fi::ceil_div(pps, BK) * BK;
-    splits = fi::ceil_div(g.P, pps);
-    fi::ProfScope prof(FI_K_CONV_WGRAD + (BMsel == 64 ? 0 : 4) + window_class(R, S), st);
-    if (BMsel == 64)
-        launch_wgrad<64>(g, x, dy, dweight, splits, pps, hwc, dbias, st, batch);
+    fi::ProfScope prof(plan.kernel_id, st);
+    if (plan.bm == 64)
+        launch_wgrad<64>(g, x, dy, dweight, plan.splits, plan.pps, hwc, dbias, st, batch);
     else
-        launch_wgrad<128>(g, x, dy, dweight, splits, pps, hwc, dbias, st, batch);
+        launch_wgrad<128>(g, x, dy, dweight, plan.splits, plan.pps, hwc, dbias, st, batch);
     FI_HIP_CHECK(hipGetLastError());
+    return FI_OK;
+}
+
+int fi_conv2d_weight_grad_plan(const float *x, const float *dy, float *dweight, int N, int Cin, int H, int W, int Cout,
+                               int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int weight_layout,
+                               float *dbias, int flags, int n, int *kernel_id)
+{
+    FI_REQUIRE(kernel_id != nullptr, "null pointer");
+    FI_REQUIRE(n >= 1, "empty batch / null pointer table");
+    ConvGeom g;
+    bool hwc;
+    const int rc = wgrad_checked(g, hwc, x, dy, dweight, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w,
+                                 weight_layout);
+    if (rc != FI_OK) return rc;
+    *kernel_id = wgrad_conv_plan(g, wgrad_batch_size(wgrad_batchable(g, x, dy, weight_layout), n, flags, true)).kernel_id;
     return FI_OK;
 }
 
@@ -2621,30 +2724,34 @@ __global__ __launch_bounds__(256) void gemm_slab_reduce_kernel(const float *__re
     }
 }
 
-static void gemm_nt_plan(int M, int N, int K, int *bm, int *splits, int *pps)
+// fi_gemm_nt's tiles and K split: the weight gradient's with Cout = M, Cin = N, pixels = K, one problem, no FI_WG_* knobs
+static WgradPlan gemm_nt_plan(int M, int N, int K)
 {
-    // the tile / split choice of fi_conv2d_weight_grad with Cout = M, Cin = N, pixels = K
-    const long max_splits0 = ((long)K + 511) / 512;
-    const long tiles128 = (long)fi::ceil_div(N, BN) * fi::ceil_div(M, 128);
-    const long per = 1024 / tiles128 < 1 ? 1 : 1024 / tiles128;
-    const long reach128 = tiles128 * (per < max_splits0 ? per : max_splits0);
-    *bm = (M <= 64 || reach128 < 768) ? 64 : 128;
-    const long tiles = (long)fi::ceil_div(N, BN) * fi::ceil_div(M, *bm);
     static const long target_wg = getenv("FI_GEMM_TARGET") ? atol(getenv("FI_GEMM_TARGET")) : 1024;      // (tuning knob)
-    long want = target_wg / tiles;
-    long sp = want < 1 ? 1 : (want > max_splits0 ? max_splits0 : want);
-    int p = fi::ceil_div(K, (int)sp);
-    p = fi::ceil_div(p, BK) * BK;
-    *pps = p;
-    *splits = fi::ceil_div(K, p);
+    return plan_wgrad(M, N, K, 1, 1, 1, 512, 0, target_wg);
+}
+
+// fi_gemm_nt_affine's argument checks -> g (all but zero, dw_slab, n_live)
+static int gemm_nt_checked(ConvGeom &g, const float *a, const float *b, const float *scale, const float *bias, const float *c,
+                           int M, int N, int K, const float *workspace)
+{
+    FI_REQUIRE(a && b && c && workspace, "null pointer");
+    FI_REQUIRE(((uintptr_t)scale & 15) == 0, "fi_gemm_nt needs 16-byte aligned operands");
+    FI_REQUIRE(M >= 1 && N >= 1 && K >= 4, "sizes must be positive");
+    FI_REQUIRE(N % BN == 0 && K % 4 == 0, "fi_gemm_nt needs N % 128 == 0 and K % 4 == 0");
+    FI_REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)workspace | (uintptr_t)bias) & 15) == 0,
+               "fi_gemm_nt needs 16-byte aligned operands");
+    FI_REQUIRE((long)M * K * 4 < 0x7fffff00L && (long)N * K * 4 < 0x7fffff00L, "operand larger than 2 GB");
+    const int rc = make_geom(g, 1, N, 1, K, M, 1, 1, 1, 1, 0, 0);
+    if (rc != FI_OK) return rc;
+    FI_REQUIRE(wgrad_same_size(g, b, a), "operands do not meet the row-major kernel's alignment rules");
+    return FI_OK;
 }
 
 size_t fi_gemm_nt_workspace_bytes(int M, int N, int K)
 {
     if (M < 1 || N < 1 || K < 1) return 0;
-    int bm, splits, pps;
-    gemm_nt_plan(M, N, K, &bm, &splits, &pps);
-    return sizeof(float) * (size_t)splits * (size_t)M * (size_t)N;
+    return sizeof(float) * (size_t)gemm_nt_plan(M, N, K).splits * (size_t)M * (size_t)N;
 }
 
 int fi_gemm_nt(const float *a, const float *b, const float *bias, float *c, int M, int N, int K, int relu,
@@ -2662,39 +2769,40 @@ int fi_gemm_nt_rows(const float *a, const float *b, const float *bias, float *c,
 int fi_gemm_nt_affine(const float *a, const float *b, const float *scale, const float *bias, float *c, int M, int N, int K,
                       int relu, float *workspace, const int32_t *m_live_dev, fi_stream_t stream)
 {
-    FI_REQUIRE(a && b && c && workspace, "null pointer");
-    FI_REQUIRE(((uintptr_t)scale & 15) == 0, "fi_gemm_nt needs 16-byte aligned operands");
-    FI_REQUIRE(M >= 1 && N >= 1 && K >= 4, "sizes must be positive");
-    FI_REQUIRE(N % BN == 0 && K % 4 == 0, "fi_gemm_nt needs N % 128 == 0 and K % 4 == 0");
-    FI_REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)workspace | (uintptr_t)bias) & 15) == 0,
-               "fi_gemm_nt needs 16-byte aligned operands");
-    FI_REQUIRE((long)M * K * 4 < 0x7fffff00L && (long)N * K * 4 < 0x7fffff00L, "operand larger than 2 GB");
     ConvGeom g;
-    int rc = make_geom(g, 1, N, 1, K, M, 1, 1, 1, 1, 0, 0);
+    const int rc = gemm_nt_checked(g, a, b, scale, bias, c, M, N, K, workspace);
     if (rc != FI_OK) return rc;
     g.zero = zero_page();
     FI_REQUIRE(g.zero != nullptr, "zero page lookup failed (no HIP device?)");
-    FI_REQUIRE(wgrad_same_size(g, b, a), "operands do not meet the row-major kernel's alignment rules");
-    int bm, splits, pps;
-    gemm_nt_plan(M, N, K, &bm, &splits, &pps);
+    const WgradPlan plan = gemm_nt_plan(M, N, K);
     g.dw_slab = (long)M * N;
     g.n_live = m_live_dev;
     hipStream_t st = (hipStream_t)stream;
     {
-        fi::ProfScope prof(FI_K_CONV_WGRAD + (bm == 64 ? 0 : 4) + window_class(1, 1), st);
-        if (bm == 64)
-            launch_wgrad<64>(g, b, a, workspace, splits, pps, true, nullptr, st);
+        fi::ProfScope prof(plan.kernel_id, st);
+        if (plan.bm == 64)
+            launch_wgrad<64>(g, b, a, workspace, plan.splits, plan.pps, true, nullptr, st);
         else
-            launch_wgrad<128>(g, b, a, workspace, splits, pps, true, nullptr, st);
+            launch_wgrad<128>(g, b, a, workspace, plan.splits, plan.pps, true, nullptr, st);
         FI_HIP_CHECK(hipGetLastError());
     }
     const long total4 = (long)M * N / 4;
     const long blocks = (total4 + 255) / 256;
     fi::ProfScope prof2(FI_K_GEMM_REDUCE, st);
     hipLaunchKernelGGL(gemm_slab_reduce_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, st, workspace,
-                       splits, g.dw_slab, bias, N, relu, c, total4, m_live_dev, bm, scale);
+                       plan.splits, g.dw_slab, bias, N, relu, c, total4, m_live_dev, plan.bm, scale);
     FI_HIP_CHECK(hipGetLastError());
     return FI_OK;
+}
+
+int fi_gemm_nt_plan(const float *a, const float *b, const float *scale, const float *bias, float *c, int M, int N, int K,
+                    int relu, float *workspace, int *kernel_id)
+{
+    FI_REQUIRE(kernel_id != nullptr, "null pointer");
+    ConvGeom g;
+    const int rc = gemm_nt_checked(g, a, b, scale, bias, c, M, N, K, workspace);
+    if (rc == FI_OK) *kernel_id = gemm_nt_plan(M, N, K).kernel_id;
+    return rc;
 }
 
 int fi_weight_transpose_batch(const FiTransposeDesc *descs_dev, int n, long total_tiles, fi_stream_t stream)

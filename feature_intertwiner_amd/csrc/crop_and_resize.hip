@@ -58,7 +58,7 @@ struct LevelSetMut {
     int n;
 };
 
-// Sampling coordinate k of one axis.  Mirrors the operation order of the
+// Sampling coordinate k of one axis.  Keeps the operation order of the
 // reference exactly (each * / + rounded to fp32; the crop == 1 case goes through
 // double because of the 0.5 literal) -- oracle: orc_axis_taps().
 // c(k) = base + (float)k * step: the two numbers the coordinate of every bin of one axis is made of.  crop == 1: the

@@ -401,10 +401,23 @@ int fi_conv2d_forward_live(const float *x, const float *weight, const float *bia
                            int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int relu,
                            int weight_layout, int out_h, int out_w, int output_layout, const int32_t *n_live_dev,
                            fi_stream_t stream);
+/* Which kernel fi_conv2d_forward_live (and so fi_conv2d_forward, _gated) runs for these arguments: writes the FI_K_* id of
+ * the launch's profiling counter to *kernel_id.  A host-only query -- no HIP call, nothing is launched, pointers are only
+ * inspected for NULL and alignment -- that runs the planner and the argument checks of the entry point itself (same status
+ * for arguments it rejects), FI_NO_PATCH / FI_NO_REG1X1 included.  For per-kernel bookkeeping (conv.FLOP_LOG). */
+int fi_conv2d_forward_plan(const float *x, const float *weight, const float *bias, const float *scale,
+                           const float *residual, const float *gate, float *y, int N, int Cin, int H, int W,
+                           int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int relu,
+                           int weight_layout, int out_h, int out_w, int output_layout, int *kernel_id);
 int fi_conv2d_weight_grad(const float *x, const float *dy, float *dweight, int N, int Cin,
                           int H, int W, int Cout, int R, int S, int stride_h, int stride_w,
                           int pad_h, int pad_w, int weight_layout, float *dbias, int flags,
                           fi_stream_t stream);
+/* The same query for fi_conv2d_weight_grad (n = 1) and for the first launch of fi_conv2d_weight_grad_batch with n problems
+ * of this geometry, x / dy / dweight being those of its first problem and dbias given for all problems or for none. */
+int fi_conv2d_weight_grad_plan(const float *x, const float *dy, float *dweight, int N, int Cin, int H, int W, int Cout,
+                               int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int weight_layout,
+                               float *dbias, int flags, int n, int *kernel_id);
 /* n weight gradients of ONE geometry (the identical residual blocks of a ResNet stage: 23 in C4 of ResNet-101,
  * lib/sub_module.py:103-116) in one launch: x[i], dy[i], dweight[i], dbias[i] (dbias NULL, or one pointer per problem)
  * are HOST arrays of device pointers.  A layer of the C4 stage at batch 4 is a single round of short workgroups whose
@@ -447,6 +460,9 @@ int fi_gemm_nt_rows(const float *a, const float *b, const float *bias, float *c,
  * and ReLU in one pass (scale NULL = fi_gemm_nt_rows). */
 int fi_gemm_nt_affine(const float *a, const float *b, const float *scale, const float *bias, float *c, int M, int N, int K,
                       int relu, float *workspace, const int32_t *m_live_dev, fi_stream_t stream);
+/* The same query for the product kernel of fi_gemm_nt / _rows / _affine (not the reduction pass, always FI_K_GEMM_REDUCE). */
+int fi_gemm_nt_plan(const float *a, const float *b, const float *scale, const float *bias, float *c, int M, int N, int K,
+                    int relu, float *workspace, int *kernel_id);
 
 /* All layers' W^T for the data-gradient kernel in one launch: for every descriptor, src is
  * [rows][taps][cols] (a weight stored [Cout][R][S][Cin]) and dst becomes [cols][taps][rows]

@@ -122,6 +122,89 @@ def test_round3_entry_points_validate_and_gradient_handoffs_on_the_host():
     assert C.GradBox().taker is False
 
 
+def _planned(query, *args):
+    import ctypes
+    from feature_intertwiner_amd import _lib
+    k = ctypes.c_int(-1)
+    rc = query(*args, ctypes.byref(k))
+    return _lib.KERNEL_KEYS[k.value] if rc == 0 else rc
+
+
+def test_plan_queries_name_the_kernel_on_both_sides_of_every_threshold():
+    """fi_conv2d_forward_plan / fi_conv2d_weight_grad_plan / fi_gemm_nt_plan are the planners of the launch entries run on the
+    host: aligned fake pointer values, shapes on both sides of every threshold of the kernel selection.  The expected keys
+    follow from the constants of csrc/conv_igemm.hip (tile counts in the comments); tests/test_gpu_conv_plan.py holds the
+    same shapes to the profiling counters of the launches on the GPU."""
+    from feature_intertwiner_amd import _lib
+    L = _lib.load()
+    X, Wt, Y, G = 0x10000, 0x20000, 0x30000, 0x40000
+
+    def fwd(N, Cin, H, W, Cout, R, stride, pad, layout, gate=None, y=Y):
+        return _planned(L.fi_conv2d_forward_plan, X, Wt, None, None, None, gate, y, N, Cin, H, W, Cout, R, R, stride, stride,
+                        pad, pad, 0, layout, 0, 0, 0)
+
+    # 3x3 / s1 / p1, tap-major, Cin 16, Cout 256: 2-D patch tiles from 256 workgroups, flat ones (14 x 14 maps) from 512
+    assert fwd(1, 16, 128, 128, 256, 3, 1, 1, 1) == "conv3x3_patch"                     # 256 tiles
+    assert fwd(1, 16, 120, 128, 256, 3, 1, 1, 1) == "conv_fwd_bm64_3x3"                 # 240
+    assert fwd(168, 16, 14, 14, 256, 3, 1, 1, 1) == "conv3x3_patch_flat"                # 516
+    assert fwd(166, 16, 14, 14, 256, 3, 1, 1, 1) == "conv_fwd_bm64_3x3"                 # 510
+    assert fwd(168, 16, 14, 14, 256, 3, 1, 1, 1, gate=G + 8) == "conv3x3_patch_flat"
+    # a gate that is 4- but not 8-byte aligned: not the flat kernel -- the generic one, whose 516 tiles take 128 rows
+    assert fwd(168, 16, 14, 14, 256, 3, 1, 1, 1, gate=G + 4) == "conv_fwd_bm128_3x3"
+    assert fwd(168, 16, 14, 14, 256, 3, 1, 1, 1, y=Y + 4) == "conv_fwd_bm128_3x3"       # ... and so for y
+    # 1x1 / s1, Cout 256: weights in registers from 256 tiles and 128 input channels; fragment-major weights: its ring form
+    assert fwd(1, 128, 128, 128, 256, 1, 1, 0, 1) == "conv1x1_reg"
+    assert fwd(1, 128, 124, 128, 256, 1, 1, 0, 1) == "conv_fwd_bm64_1x1"                # 248 tiles
+    assert fwd(1, 96, 128, 128, 256, 1, 1, 0, 1) == "conv_fwd_bm64_1x1"                 # Cin < 128
+    assert fwd(1, 128, 128, 128, 256, 1, 1, 0, 3) == "conv1x1_reg"
+    # generic tile height, 3x3 / s2 / p1: 128 rows from 512 tiles of 128 x 128; narrow layers always 64
+    assert fwd(1, 16, 512, 256, 256, 3, 2, 1, 1) == "conv_fwd_bm128_3x3"                # 512
+    assert fwd(1, 16, 508, 256, 256, 3, 2, 1, 1) == "conv_fwd_bm64_3x3"                 # 508
+    assert fwd(2, 3, 64, 64, 64, 7, 2, 3, 0) == "conv_fwd_bm64_7x7"
+
+    # weight gradient 1x1, Cin 1024, Cout 256, 64 x 64 maps: 16 tiles of 128 rows x ceil(pixels / 512) splits x batch >= 768
+    def wgrad(N, n, flags=_lib.OUTPUTS_ZEROED, x=X):
+        return _planned(L.fi_conv2d_weight_grad_plan, x, Y, Wt, N, 1024, 64, 64, 256, 1, 1, 1, 1, 0, 0, 1, None, flags, n)
+
+    assert wgrad(6, 1) == "conv_wgrad_bm128_1x1" and wgrad(5, 1) == "conv_wgrad_bm64_1x1"
+    assert wgrad(6, 1, flags=0) == "conv_wgrad_bm128_1x1"
+    assert wgrad(1, 6) == "conv_wgrad_bm128_1x1" and wgrad(1, 5) == "conv_wgrad_bm64_1x1"
+    # what fi_conv2d_weight_grad_batch cannot put into one launch runs problem by problem: the single launch's tiles
+    assert wgrad(1, 6, flags=0) == "conv_wgrad_bm64_1x1" and wgrad(1, 6, x=X + 4) == "conv_wgrad_bm64_1x1"
+
+    # the GEMM on the same tile counts (M = Cout, N = Cin, K = pixels), and its workspace: splits x M x N floats
+    def gemm(M, N, K, a=X):
+        return _planned(L.fi_gemm_nt_plan, a, Wt, None, None, Y, M, N, K, 0, G)
+
+    assert gemm(256, 1024, 24576) == "conv_wgrad_bm128_1x1" and gemm(256, 1024, 20480) == "conv_wgrad_bm64_1x1"
+    assert gemm(64, 1024, 24576) == "conv_wgrad_bm64_1x1"
+    mb = 4 * 256 * 1024
+    assert L.fi_gemm_nt_workspace_bytes(256, 1024, 24576) == 48 * mb
+    assert L.fi_gemm_nt_workspace_bytes(256, 1024, 20480) == 32 * mb
+    assert L.fi_gemm_nt_workspace_bytes(2048, 1024, 12544) == 8 * 4 * 2048 * 1024
+    assert L.fi_gemm_nt_workspace_bytes(1408, 1024, 25088) == 11 * 4 * 1408 * 1024
+
+    # an argument the launch entry rejects is rejected by the query, with the same status (and before any HIP call)
+    a = [16, 16, None, None, None, 32, 16]
+    for tail in ((1, 32, 8, 8, 64, 3, 3, 1, 1, 1, 1, 0, 5, 0, 0, 0),           # weight_layout
+                 (1, 32, 8, 8, 64, 3, 3, 1, 1, 1, 1, 0, 1, 0, 0, 2),           # output_layout
+                 (1, 30, 8, 8, 64, 3, 3, 1, 1, 1, 1, 0, 1, 0, 0, 0),           # tap-major needs Cin % 16
+                 (1, 32, 8, 8, 64, 1, 1, 1, 1, 0, 0, 0, 1, 0, 0, 1),           # gate + channels-last output
+                 (1, 64, 8, 8, 64, 1, 1, 1, 1, 0, 0, 0, 3, 0, 0, 0),           # ring weights on an ineligible shape
+                 (0, 32, 8, 8, 64, 3, 3, 1, 1, 1, 1, 0, 1, 0, 0, 0)):          # empty batch
+        assert _planned(L.fi_conv2d_forward_plan, *a, *tail) == L.fi_conv2d_forward_live(*a, *tail, None, None) == -1, tail
+    assert _planned(L.fi_conv2d_forward_plan, None, *a[1:], 1, 32, 8, 8, 64, 3, 3, 1, 1, 1, 1, 0, 1, 0, 0, 0) == -1
+    w = (16, 16, 16, 1, 32, 8, 8, 64, 3, 3, 1, 1, 1, 1, 1, None, 0)            # tap-major dW needs Cin % 128 (or Cin == 64)
+    assert _planned(L.fi_conv2d_weight_grad_plan, *w, 1) == L.fi_conv2d_weight_grad(*w, None) == -1
+    assert b"weight_layout 1" in L.fi_last_error()
+    assert _planned(L.fi_conv2d_weight_grad_plan, *w[:14], 0, None, 0, 0) == -1                      # n < 1
+    for g in ((16, 16, None, None, 16, 8, 100, 64, 0, 16),                     # N % 128
+              (16, 16, None, None, 16, 8, 128, 62, 0, 16),                     # K % 4
+              (16, 16, 8, None, 16, 8, 128, 64, 0, 16),                        # scale not 16-byte aligned
+              (16, 16, None, None, 16, 8, 128, 64, 0, None)):                  # no workspace
+        assert _planned(L.fi_gemm_nt_plan, *g) == L.fi_gemm_nt_affine(*g, None, None) == -1, g
+
+
 def test_reference_shaped_python_surface():
     import inspect
     from feature_intertwiner_amd.roi_align.crop_and_resize import CropAndResizeFunction

@@ -88,6 +88,7 @@ def test_configs2_full_size_two_steps_operators_vs_oracle(oracle):
     # Python-side bookkeeping (bench.py's per-kernel flops) agrees with what the library launched
     for key in ("conv3x3_patch", "conv3x3_patch_flat", "conv1x1_reg"):
         assert key in used and used[key][0] > 0, (key, sorted(used))
+    for key in used:
         launches, _ = _lib.prof_get(key)
         assert launches == used[key][0], (key, launches, used[key][0])
     flops = {k: v[1] for k, v in used.items()}

@@ -66,7 +66,7 @@ for _t in ("bf16", "f16"):
 def recorded_entry(name):
     """The launches the replay covers: every fi_conv* / fi_gemm_nt* entry except the host-side queries."""
     return (name.startswith("fi_conv") or name.startswith("fi_gemm_nt")) and \
-        not name.endswith("_eligible") and not name.endswith("_workspace_bytes")
+        not name.endswith("_eligible") and not name.endswith("_workspace_bytes") and not name.endswith("_plan")
 
 
 def lowp_dtype(name):
@@ -419,7 +419,7 @@ def test_step_conv_launches_match_fp64_elementwise(label, kw, size, bs):
     fams = collections.Counter(SPECS[n][0] for n in count)
     assert fams["wgrad"] + fams["wgrad_batch"] > 0 and fams["fwd"] > 0, count
     if "fp32" in label:
-        for n in ("fi_conv2d_forward_gated", "fi_conv2d_weight_grad", "fi_conv2d_weight_grad_batch", "fi_gemm_nt_affine"):
+        for n in ("fi_conv2d_forward_live", "fi_conv2d_weight_grad", "fi_conv2d_weight_grad_batch", "fi_gemm_nt_affine"):
             assert count[n] > 0, (n, count)
     else:
         t = "bf16" if "bf16" in label else "f16"
