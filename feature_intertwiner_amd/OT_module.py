@@ -61,8 +61,10 @@ class _SinkhornLoss(torch.autograd.Function):
         else:
             # d|x_i - y_j| / dx_i = (x_i - y_j) / |x_i - y_j|, and 0 at coincident points (the subgradient
             # torch.norm's backward uses); dividing by a clamped distance instead would weight the
-            # (x_i - y_j) = 0 pairs -- every pair of ReLU-dead critic outputs -- by P / 1e-30
-            dist = torch.cdist(x, y)
+            # (x_i - y_j) = 0 pairs -- every pair of ReLU-dead critic outputs -- by P / 1e-30.  The distances come
+            # from the differences, as the kernel computes its cost: cdist's default for more than 25 samples is
+            # |x|^2 + |y|^2 - 2 <x, y>, whose cancellation leaves a pair 1e-3 apart with a distance off by tens of percent
+            dist = torch.cdist(x, y, compute_mode="donot_use_mm_for_euclid_dist")
             w = torch.where(dist > 0, plan / dist.clamp_min(1e-30), torch.zeros_like(plan))
             gx = (w.sum(2, keepdim=True) * x - torch.bmm(w, y)) * g
             gy = (w.sum(1).unsqueeze(2) * y - torch.bmm(w.transpose(1, 2), x)) * g

@@ -11,7 +11,11 @@ The bar.  For an element i that sums n_i products, an fp32 kernel that accumulat
     |got_i - ref_i| <= 2^-24 * (4 * sqrt(n_i) + 16) * m_i
 of the exact value, where m_i is the same reference evaluated on absolute values (|x|, |w|, |scale|, |bias|,
 |residual|; |G| for a crop).  It bounds each element by its OWN magnitude, so a wrong small element fails it -- a bar
-relative to max|ref| lets it pass."""
+relative to max|ref| lets it pass.
+
+Further down: the references of the BatchNorm / glue / SGD launches (tests/test_gpu_step_glue_replay.py) and of the loss
+and statistics kernels -- the five detector losses, the per-class means, the meta-loss statistics, Sinkhorn
+(tests/test_gpu_loss_kernels.py)."""
 import math
 
 import numpy as np
@@ -384,3 +388,208 @@ def sgd_ref(p, g, buf, coef, wd, mom, lr):
     else:
         b, mb = u, mu
     return p - lr * b, b, gs, p.abs() + lr * mb, mb, gs.abs()
+
+
+# ---- the five detector losses (fi_detector_losses) ---------------------------------------------------------------------
+def _t64(a, device=None):
+    t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+    return t.to(device=device if device is not None else t.device, dtype=torch.float64)
+
+
+def _smooth_l1(d):
+    a = d.abs()
+    return torch.where(a < 1.0, 0.5 * d * d, a - 0.5), torch.where(a < 1.0, d, torch.sign(d))
+
+
+def _lse_rows(lg):
+    mx = lg.max(1, keepdim=True)[0]
+    e = torch.exp(lg - mx)
+    se = e.sum(1, keepdim=True)
+    return (mx + torch.log(se)).squeeze(1), e / se
+
+
+def detector_losses_ref(rpn_match, rpn_deltas, row_image, row_anchor, row_logits, row_bbox, roi_cls, cls_logits, roi_deltas,
+                        roi_bbox, mask_cls, mask_logits, mask_targets):
+    """fi_detector_losses in float64 (include/fi_capi.h, csrc/losses.hip; lib/layers.py:808-934 of the reference).
+    rpn_match [b,A], rpn_deltas [b,A,4], row_image / row_anchor [Rr] (-1: padding row), row_logits [Rr,2], row_bbox [Rr,4],
+    roi_cls [N], cls_logits [N,K], roi_deltas [N,4], roi_bbox [N,K,4], mask_cls [Nm], mask_logits [Nm,2,2,h,w] (the target
+    class's channel before the pixel shuffle), mask_targets [Nm,2h,2w].
+    Returns (losses [5], factors [5] = d loss / d stored gradient = 1 / count (0 for the switched-off class loss), the five
+    UNNORMALISED gradient tensors, counts [4] = rows with match != 0, RPN positives, RoI positives, positive mask rows).
+    Padding rows, rows that do not enter a loss, the box rows off the target class and non-positive mask rows have an
+    exactly zero gradient; the class-logit gradient is softmax - onehot on every RoI whether or not the loss is on."""
+    dev = row_logits.device if torch.is_tensor(row_logits) else None
+    T = lambda a: _t64(a, dev)
+    I = lambda a: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(device=dev).long()
+    match, deltas, rl, rb = T(rpn_match), T(rpn_deltas), T(row_logits), T(row_bbox)
+    im, an = I(row_image), I(row_anchor)
+    valid = im >= 0
+    i0, a0 = im.clamp(min=0), an.clamp(min=0)
+    m = torch.where(valid, match[i0, a0], torch.zeros_like(rl[:, 0]))
+    on, pos = (m != 0).to(torch.float64), (m == 1).to(torch.float64)
+    lse, p = _lse_rows(rl)
+    onehot = torch.stack((1.0 - pos, pos), 1)
+    n_rpn, n_rpn_pos = on.sum(), pos.sum()
+    l_rpn_cls = (on * (lse - (rl * onehot).sum(1))).sum() / n_rpn.clamp(min=1)
+    g_row_logits = on[:, None] * (p - onehot)
+    tgt = torch.where(valid[:, None], deltas[i0, a0], torch.zeros_like(rb))
+    v, g = _smooth_l1(rb - tgt)
+    l_rpn_box = (pos[:, None] * v).sum() / (4.0 * n_rpn_pos).clamp(min=1)
+    g_row_bbox = pos[:, None] * g
+
+    cl, rd, rbb = T(cls_logits), T(roi_deltas), T(roi_bbox)
+    t = I(roi_cls)
+    N, K = cl.shape
+    lse, p = _lse_rows(cl)
+    oh = torch.zeros_like(cl)
+    oh[torch.arange(N, device=cl.device), t] = 1.0
+    fg = (t > 0).to(torch.float64)
+    n_fg = fg.sum()
+    has_fg = (n_fg > 0).to(torch.float64)
+    l_cls = (lse - (cl * oh).sum(1)).sum() / N * has_fg
+    g_cls = p - oh
+    v, g = _smooth_l1(rbb[torch.arange(N, device=cl.device), t] - rd)                    # [N,4]: the target class's row
+    l_box = (fg[:, None] * v).sum() / (4.0 * n_fg).clamp(min=1)
+    g_box = torch.zeros_like(rbb)
+    g_box[torch.arange(N, device=cl.device), t] = fg[:, None] * g
+
+    ml, mt = T(mask_logits), T(mask_targets)
+    Nm, _, _, h, w = ml.shape
+    mpos = (I(mask_cls) > 0).to(torch.float64)
+    # the pixel shuffle of the TARGET: logits [a][b][y][x] face target[2y + a][2x + b]  (ab >> 1 = a, ab & 1 = b)
+    tu = mt.reshape(Nm, h, 2, w, 2).permute(0, 2, 4, 1, 3)
+    pr, q = 1.0 / (1.0 + torch.exp(-ml)), 1.0 / (1.0 + torch.exp(ml))            # sigmoid and 1 - sigmoid
+    lp, lq = torch.log(pr).clamp(min=-100.0), torch.log(q).clamp(min=-100.0)      # F.binary_cross_entropy's clamp
+    bce = -(tu * lp + (1.0 - tu) * lq)
+    n_mask = mpos.sum()
+    l_mask = (mpos.view(-1, 1, 1, 1, 1) * bce).sum() / (n_mask * 4 * h * w).clamp(min=1)
+    # BCE's backward (p - t) / max((1 - p) p, 1e-12) times the sigmoid's p (1 - p)
+    g_mask = mpos.view(-1, 1, 1, 1, 1) * ((pr - tu) / (q * pr).clamp(min=1e-12) * (pr * q))
+
+    one = torch.ones((), dtype=torch.float64, device=rl.device)
+    losses = torch.stack((l_rpn_cls, l_rpn_box, l_cls, l_box, l_mask))
+    factors = torch.stack((one / n_rpn.clamp(min=1), one / (4.0 * n_rpn_pos).clamp(min=1), has_fg / N,
+                           one / (4.0 * n_fg).clamp(min=1), one / (n_mask * 4 * h * w).clamp(min=1)))
+    counts = torch.stack((n_rpn, n_rpn_pos, n_fg, n_mask))
+    return losses, factors, [g_row_logits, g_row_bbox, g_cls, g_box, g_mask], counts
+
+
+# ---- per-class means (fi_class_mean_forward / _backward) ----------------------------------------------------------------
+def class_mean_ref(features, gt, K):
+    """features [N,F], gt [N] -> feat [F,K] (column c = mean of the rows with label c, 0 < c < K; zero when the class has
+    no row), cnt [K], and for the bar the per-class sum |x| [F,K] and the row count (= cnt).  Labels outside (0, K)
+    -- background, negative, >= K -- contribute nothing."""
+    x = _t64(features)
+    g = (gt if torch.is_tensor(gt) else torch.from_numpy(np.ascontiguousarray(gt))).to(x.device).long().reshape(-1)
+    N, F_ = x.shape
+    ok = (g > 0) & (g < K)
+    idx = g[ok]
+    s = torch.zeros((K, F_), dtype=torch.float64, device=x.device).index_add_(0, idx, x[ok])
+    sa = torch.zeros((K, F_), dtype=torch.float64, device=x.device).index_add_(0, idx, x[ok].abs())
+    cnt = torch.zeros(K, dtype=torch.float64, device=x.device).index_add_(0, idx, torch.ones_like(idx, dtype=torch.float64))
+    feat = torch.where(cnt[:, None] > 0, s / cnt.clamp(min=1)[:, None], torch.zeros_like(s))
+    return feat.t().contiguous(), cnt, sa.t().contiguous(), cnt.clone()
+
+
+def class_mean_bwd_ref(grad_feat, gt, cnt, K):
+    """grad_features [N,F] = grad_feat[:, gt[n]] / cnt[gt[n]] for 0 < gt[n] < K (and cnt > 0), exactly 0 otherwise."""
+    gf, c = _t64(grad_feat), _t64(cnt).reshape(-1)
+    g = (gt if torch.is_tensor(gt) else torch.from_numpy(np.ascontiguousarray(gt))).to(gf.device).long().reshape(-1)
+    ok = (g > 0) & (g < K)
+    gc = g.clamp(0, K - 1)
+    ok = ok & (c[gc] > 0)
+    out = gf.t()[gc] / c[gc].clamp(min=1)[:, None]
+    return torch.where(ok[:, None], out, torch.zeros_like(out))
+
+
+# ---- the statistics side of the meta loss (fi_meta_stats_*) ---------------------------------------------------------------
+META_EPS = 1e-20
+
+
+def meta_stats_ref(big_feat, big_cnt, small_feat, small_cnt, buffer, buffer_cnt):
+    """fi_meta_stats_forward (= _sums + _from_sums on one rank) in float64.  big_feat / small_feat: LOGICAL [G,S,F,K]
+    tensors (any strides), big_cnt / small_cnt [G,S,K] (or [G,S,1,K]), buffer [F,K] and buffer_cnt [K]: the history
+    BEFORE the step.  Returns a dict: the merged means b_feat / s_feat [F,K] and counts b_cnt / s_cnt [K]; active (the
+    step has small-object statistics: the count-weighted small sums do not add up to 0); the history after the step
+    buffer / buffer_cnt (the old one when not active); SMALL / BIG [K-1,F] (foreground classes, transposed); on [K-1];
+    and the magnitudes m_b_feat, m_s_feat, m_buffer for the bar (the same formulas on absolute values)."""
+    bf, sf = _t64(big_feat), _t64(small_feat)
+    G, S, F_, K = bf.shape
+    bc, sc = _t64(big_cnt).reshape(G, S, 1, K), _t64(small_cnt).reshape(G, S, 1, K)
+    buf, oc = _t64(buffer).reshape(F_, K), _t64(buffer_cnt).reshape(K)
+
+    def merged(f, c):
+        s, a, n = (f * c).sum((0, 1)), (f * c).abs().sum((0, 1)), c.sum((0, 1)).reshape(K)
+        return s / (n + META_EPS), a / (n + META_EPS), n, s
+    b_feat, m_b, b_cnt, _ = merged(bf, bc)
+    s_feat, m_s, s_cnt, s_sum = merged(sf, sc)
+    active = bool(s_sum.sum() != 0)
+    if active:
+        nc = oc + b_cnt
+        new_buf = (buf * oc + b_feat * b_cnt) / (nc + META_EPS)
+        m_buf = (buf.abs() * oc + m_b * b_cnt) / (nc + META_EPS)
+    else:
+        nc, new_buf, m_buf = oc, buf, buf.abs()
+    on = ((s_cnt > 0) & (nc > 0))[1:].to(torch.float64)
+    return dict(b_feat=b_feat, s_feat=s_feat, b_cnt=b_cnt, s_cnt=s_cnt, active=active, buffer=new_buf, buffer_cnt=nc,
+                SMALL=s_feat[:, 1:].t().contiguous(), BIG=new_buf[:, 1:].t().contiguous(), on=on,
+                m_b_feat=m_b, m_s_feat=m_s, m_buffer=m_buf)
+
+
+def meta_stats_bwd_ref(dsmall, s_cnt, small_cnt):
+    """fi_meta_stats_backward: d small_feat [G,S,F,K] = dsmall[k-1][f] / (s_cnt[k] + eps) * small_cnt[g][s][k], 0 for the
+    background class k = 0.  dsmall [K-1,F], s_cnt [K] (the merged small counts), small_cnt [G,S,K]."""
+    d, c = _t64(dsmall), _t64(s_cnt).reshape(-1)
+    K = c.numel()
+    sc = _t64(small_cnt)
+    G, S = sc.shape[:2]
+    sc = sc.reshape(G, S, 1, K)
+    per = torch.zeros((d.shape[1], K), dtype=torch.float64, device=d.device)
+    per[:, 1:] = d.t() / (c[1:] + META_EPS)
+    return per[None, None] * sc
+
+
+# ---- Sinkhorn (fi_sinkhorn_forward, OT_module.sinkhorn_loss) --------------------------------------------------------------
+OT_EPS = 1e-20
+
+
+def _ot_cost(x, y, mode):
+    """mode 0: 1 - <x / (|x| + eps), y / (|y| + eps)>; 1: |x_i - y_j| (zero subgradient at coincident points, as
+    torch.norm's); 2: 1 - <x, y> on rows the caller normalised."""
+    if mode == 0:
+        x = x / (x.norm(dim=1, keepdim=True) + OT_EPS)
+        y = y / (y.norm(dim=1, keepdim=True) + OT_EPS)
+    if mode == 1:
+        ss = ((x[:, None, :] - y[None, :, :]) ** 2).sum(2)
+        return torch.where(ss > 0, torch.sqrt(torch.where(ss > 0, ss, torch.ones_like(ss))), torch.zeros_like(ss))
+    return 1.0 - x @ y.t()
+
+
+def _ot_plan(C, eps_inv, L):
+    K = torch.exp(-eps_inv * C)
+    S = C.shape[0]
+    u = torch.full((S, 1), 1.0 / S, dtype=torch.float64, device=C.device)
+    a = b = u
+    for _ in range(L):
+        a = u / (K @ b + OT_EPS)
+        b = u / (K.t() @ a + OT_EPS)
+    return a * K * b.t()
+
+
+def sinkhorn_ref(x, y, eps_inv, L, mode):
+    """One problem of lib/OT_module.py:104-135 in float64: x, y [S,D]; eps_inv = 1 / epsilon as the C ABI takes it; L
+    iterations from a = b = 1/S; returns (loss = <P, C>, plan P [S,S])."""
+    C = _ot_cost(_t64(x), _t64(y), mode)
+    P = _ot_plan(C, float(eps_inv), int(L))
+    return (P * C).sum(), P
+
+
+def sinkhorn_detached_plan_loss(x, y, eps_inv, L, form):
+    """The differentiable loss of OT_module.sinkhorn_loss on float64 tensors x, y [P,S,D] (they may require grad):
+    loss[p] = <P_p.detach(), C_p(x, y)>, form 'cosine' (out-of-place normalisation) or 'l2'."""
+    mode = {"cosine": 0, "l2": 1}[form]
+    out = []
+    for p in range(x.shape[0]):
+        C = _ot_cost(x[p], y[p], mode)
+        out.append((_ot_plan(C, float(eps_inv), int(L)).detach() * C).sum())
+    return torch.stack(out)

@@ -352,3 +352,238 @@ def test_sgd_ref_equals_torch_clip_and_sgd_and_rejects_a_missing_clip(momentum):
         R.check_bar(rp.float(), rp, mp, 1)
         bad = R.sgd_ref(p, gr, b if momentum else None, 1.0, wd, momentum, 0.02)[0]       # the clip factor left out
         _fails(lambda: R.check_bar(bad, rp, mp, 1))
+
+
+# ---- loss and statistics references (tests/test_gpu_loss_kernels.py) -----------------------------------------------------
+def _loss_case(seed, b=2, A=40, Rr=37, N=9, K=7, Nm=5, h=3, w=4):
+    g = torch.Generator().manual_seed(seed)
+    match = torch.zeros(b, A, dtype=D)
+    deltas = torch.zeros(b, A, 4, dtype=D)
+    im = torch.randint(0, b, (Rr,), generator=g)
+    an = torch.randperm(A, generator=g)[:Rr] if Rr <= A else torch.randint(0, A, (Rr,), generator=g)
+    im[torch.rand(Rr, generator=g) < 0.3] = -1                                   # padding rows, interleaved
+    an[im < 0] = -1
+    v = im >= 0
+    kind = torch.randint(0, 2, (Rr,), generator=g).to(D) * 2 - 1                 # +1 / -1
+    match[im[v], an[v]] = kind[v]
+    deltas[im[v], an[v]] = torch.randn(int(v.sum()), 4, generator=g, dtype=D) * (kind[v] == 1)[:, None]
+    ids = torch.randint(0, K, (N,), generator=g)
+    ids[0] = 0
+    mids = torch.randint(0, 2, (Nm,), generator=g) * torch.randint(1, K, (Nm,), generator=g)
+    mk = lambda *s: (torch.randn(*s, generator=g, dtype=D) * 2).requires_grad_(True)
+    return dict(match=match, deltas=deltas, im=im, an=an, ids=ids, mids=mids,
+                tdel=torch.randn(N, 4, generator=g, dtype=D) * (ids > 0)[:, None],
+                tmask=(torch.rand(Nm, 2 * h, 2 * w, generator=g) > 0.5).to(D),
+                row_logits=mk(Rr, 2), row_bbox=mk(Rr, 4), cls_logits=mk(N, K), roi_bbox=mk(N, K, 4),
+                mask_logits=mk(Nm, 2, 2, h, w))
+
+
+def _layers_five(c, ids=None, mids=None):
+    """The five loss functions of layers.py on the case's tensors (whatever their dtype and device)."""
+    from feature_intertwiner_amd import layers as L
+    ids = c["ids"] if ids is None else ids
+    mids = c["mids"] if mids is None else mids
+    rc, rb = L.compute_rpn_losses_on_rows(c["match"], c["deltas"], c["im"], c["an"], c["im"] >= 0, c["row_logits"],
+                                          c["row_bbox"])
+    return [rc, rb, L.compute_mrcnn_class_loss(ids[None], c["cls_logits"][None]),
+            L.compute_mrcnn_bbox_loss(c["tdel"][None], ids[None], c["roi_bbox"][None]),
+            L.compute_mrcnn_mask_loss_selected(c["tmask"][None], mids[None], c["mask_logits"][None])]
+
+
+def _ref_of_case(c, ids=None, mids=None):
+    d = lambda t: t.detach()
+    return R.detector_losses_ref(c["match"], c["deltas"], c["im"], c["an"], d(c["row_logits"]), d(c["row_bbox"]),
+                                 c["ids"] if ids is None else ids, d(c["cls_logits"]), c["tdel"], d(c["roi_bbox"]),
+                                 c["mids"] if mids is None else mids, d(c["mask_logits"]), c["tmask"])
+
+
+@pytest.mark.parametrize("fg", [True, False])
+def test_detector_losses_ref_equals_the_loss_functions_in_float64(fg):
+    """Values and gradients (autograd) of layers.py's five loss functions run in float64: the stored gradients times
+    their factors are the gradients of the losses; padding rows, rows off the target class and non-positive mask rows
+    are exactly zero; without any foreground the class loss and its factor are 0 while softmax - onehot stays stored."""
+    c = _loss_case(11)
+    ids = c["ids"] if fg else torch.zeros_like(c["ids"])
+    mids = c["mids"] if fg else torch.zeros_like(c["mids"])
+    outs = ("row_logits", "row_bbox", "cls_logits", "roi_bbox", "mask_logits")
+    five = _layers_five(c, ids, mids)
+    losses, factors, grads, counts = _ref_of_case(c, ids, mids)
+    for k, (lv, name) in enumerate(zip(five, outs)):
+        (gr,) = torch.autograd.grad(lv, c[name])
+        lv = lv.detach()
+        assert abs(float(lv) - float(losses[k])) <= 1e-12 * max(1.0, abs(float(lv))), (k, float(lv), float(losses[k]))
+        assert float((grads[k] * factors[k] - gr.reshape(grads[k].shape)).abs().max()) <= 1e-12
+    pad = c["im"] < 0
+    assert int(pad.sum()) > 0 and float(grads[0][pad].abs().max()) == 0 and float(grads[1][pad].abs().max()) == 0
+    assert float(counts[0]) == float((c["im"] >= 0).sum())
+    off = torch.ones_like(grads[3], dtype=torch.bool)
+    off[torch.arange(len(ids)), ids] = False
+    assert float(grads[3][off].abs().max()) == 0 and float(grads[3][ids == 0].abs().max()) == 0
+    assert float(grads[4][mids == 0].abs().max()) == 0
+    if fg:
+        assert float(counts[2]) == float((ids > 0).sum()) > 0 and float(counts[3]) == float((mids > 0).sum()) > 0
+    else:
+        assert [float(v) for v in losses[2:]] == [0.0, 0.0, 0.0] and float(factors[2]) == 0.0
+        assert float(factors[3]) == 1.0 and float(factors[4]) == 1.0 and float(grads[2].abs().max()) > 0
+
+
+def test_detector_losses_ref_smooth_l1_edges_and_the_target_shuffle():
+    """|d| == 1, d == 0 and |d| just below 1 take the documented branch, and the mask target is read at
+    [2y + a][2x + b]: a target that is 1 on exactly one pixel moves exactly one logit's loss term."""
+    c = _loss_case(12, Rr=6, N=1, Nm=1, h=2, w=3)
+    z = torch.zeros(1, 4, dtype=D)
+    d = torch.tensor([[1.0, -1.0, 0.0, 1.0 - 2.0 ** -24]], dtype=D)
+    ids = torch.tensor([3])
+    box = torch.zeros(1, 7, 4, dtype=D)
+    box[0, 3] = d
+    out = R.detector_losses_ref(c["match"], c["deltas"], c["im"], c["an"], c["row_logits"].detach(), c["row_bbox"].detach(),
+                                ids, c["cls_logits"].detach()[:1], z, box, torch.tensor([2]),
+                                torch.zeros(1, 2, 2, 2, 3, dtype=D), torch.zeros(1, 4, 6, dtype=D))
+    assert torch.equal(out[2][3][0, 3], torch.tensor([1.0, -1.0, 0.0, 1.0 - 2.0 ** -24], dtype=D))
+    assert abs(float(out[0][3]) - (0.5 + 0.5 + 0.0 + 0.5 * (1.0 - 2.0 ** -24) ** 2) / 4) <= 1e-15
+    base = float(out[0][4])
+    assert abs(base - np.log(2.0)) <= 1e-15
+    for (a, b, y, x) in ((0, 1, 1, 2), (1, 0, 0, 1)):
+        tm = torch.zeros(1, 4, 6, dtype=D)
+        tm[0, 2 * y + a, 2 * x + b] = 1.0
+        lg = torch.zeros(1, 2, 2, 2, 3, dtype=D)
+        lg[0, a, b, y, x] = 3.0                                  # the logit facing the set pixel: its term becomes -log p
+        got = R.detector_losses_ref(c["match"], c["deltas"], c["im"], c["an"], c["row_logits"].detach(),
+                                    c["row_bbox"].detach(), ids, c["cls_logits"].detach()[:1], z, box, torch.tensor([2]),
+                                    lg, tm)
+        exp = (23 * np.log(2.0) + np.log1p(np.exp(-3.0))) / 24
+        assert abs(float(got[0][4]) - exp) <= 1e-15, (a, b, y, x)
+        assert abs(float(got[2][4][0, a, b, y, x]) - (1 / (1 + np.exp(-3.0)) - 1.0)) <= 1e-15
+
+
+def test_detector_losses_ref_returns_the_reference_values(golden_dir):
+    """On the inputs of tests/golden/layers.npz, re-laid as the kernel reads them (rows of the non-zero anchors, the mask
+    probabilities as un-shuffled logits of the target class): the five values the reference's loss functions returned.
+    The fixture holds float32 results, so the bar is float32's (2e-6, as the existing tests of these values)."""
+    import os
+    from helpers import golden_loss_inputs
+    gold = np.load(os.path.join(golden_dir, "layers.npz"))
+    li = golden_loss_inputs()
+    match = li["rpn_match"]
+    B, A = match.shape
+    per_anchor = np.zeros((B, A, 4), np.float32)
+    rows = []
+    for b in range(B):
+        pos = np.nonzero(match[b] == 1)[0]
+        per_anchor[b, pos] = li["rpn_bbox_target"][b, :len(pos)]
+        nz = np.nonzero(match[b])[0]
+        rows += [(b, a) for a in nz] + [(-1, -1)] * 5
+    im, an = np.array(rows, np.int64).T
+    ids = li["cls_ids"]
+    Rn = ids.shape[1]
+    p = li["mask_pred"].astype(np.float64)
+    sel = np.take_along_axis(p, ids.reshape(B, Rn, 1, 1, 1).astype(np.int64), 2)[:, :, 0]
+    logit = np.log(sel) - np.log1p(-sel)
+    un = logit.reshape(B * Rn, 14, 2, 14, 2).transpose(0, 2, 4, 1, 3)
+    losses = R.detector_losses_ref(match.astype(np.float64), per_anchor, im, an,
+                                   li["rpn_logits"][np.maximum(im, 0), np.maximum(an, 0)],
+                                   li["rpn_bbox_pred"][np.maximum(im, 0), np.maximum(an, 0)], ids.reshape(-1),
+                                   li["cls_logits"].reshape(B * Rn, -1), li["bbox_target"].reshape(-1, 4),
+                                   li["bbox_pred"].reshape(B * Rn, -1, 4), ids.reshape(-1), un,
+                                   li["mask_target"].reshape(B * Rn, 28, 28))[0]
+    names = ("loss_rpn_class", "loss_rpn_bbox", "loss_mrcnn_class", "loss_mrcnn_bbox", "loss_mrcnn_mask")
+    for v, k in zip(losses, names):
+        assert abs(float(v) - float(gold[k])) <= 2e-6 * max(1.0, abs(float(gold[k]))), (k, float(v), float(gold[k]))
+
+
+def test_class_mean_ref_equals_the_oracle_and_the_bar_rejects_a_dropped_row(oracle):
+    rs = np.random.RandomState(5)
+    N, F_, K = 300, 37, 50
+    x = rs.standard_normal((N, F_)).astype(np.float32)
+    gt = rs.randint(-3, K + 8, N).astype(np.int32)
+    gt[gt == 7] = 8                                              # an empty class
+    ef, ec = oracle.class_mean(x, gt, K)
+    feat, cnt, sa, rows = R.class_mean_ref(x, gt, K)
+    assert np.array_equal(cnt.numpy(), ec[0].astype(np.float64)) and float(cnt[7]) == 0 and float(cnt[0]) == 0
+    assert float(feat[:, 7].abs().max()) == 0 and float(feat[:, 0].abs().max()) == 0
+    mag = sa / rows.clamp(min=1)[None]
+    R.check_bar(torch.from_numpy(ef), feat, mag, rows[None].clamp(min=1).expand_as(feat), "oracle class mean")
+    # fp32 sums of all rows of the class but one fail it
+    c = int(torch.argmax(cnt))
+    keep = np.nonzero(gt == c)[0][1:]
+    bad = torch.from_numpy(ef).clone()
+    bad[:, c] = torch.from_numpy(x[keep].sum(0) / float(cnt[c]))
+    assert R.bar_ratio(bad, feat, mag, rows[None].clamp(min=1).expand_as(feat))[1] > 1.0
+    # the backward is the adjoint: autograd through a dense float64 restatement
+    xd = torch.from_numpy(x).double().requires_grad_(True)
+    g = torch.from_numpy(gt).long()
+    ok = (g > 0) & (g < K)
+    oh = torch.zeros(N, K, dtype=D)
+    oh[torch.arange(N)[ok], g[ok]] = 1.0
+    dense = (xd.t() @ oh) / oh.sum(0).clamp(min=1)
+    _close(feat, dense.detach())
+    w = torch.from_numpy(rs.standard_normal((F_, K)))
+    (dense * w).sum().backward()
+    got = R.class_mean_bwd_ref(w, gt, cnt, K)
+    _close(got, xd.grad)
+    assert float(got[~ok].abs().max()) == 0
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("S,Dm,L", [(9, 3, 5), (33, 17, 1), (40, 1, 50)])
+def test_sinkhorn_ref_equals_the_oracle(oracle, S, Dm, L, mode):
+    rs = np.random.RandomState(S + Dm)
+    x = rs.standard_normal((S, Dm)).astype(np.float32)
+    y = rs.standard_normal((S, Dm)).astype(np.float32)
+    if Dm == 1:
+        x, y = np.maximum(x, 0), np.maximum(y, 0)
+    v, pl = oracle.sinkhorn(x, y, 1.0, L, "l2" if mode else "cosine", return_plan=True)
+    loss, plan = R.sinkhorn_ref(x, y, 1.0, L, mode)
+    assert abs(float(loss) - float(v)) <= 1e-5 * abs(float(loss)) + 1e-9
+    assert np.allclose(pl, plan.numpy(), rtol=1e-4, atol=1e-10)
+    if mode == 0:                                                 # mode 2 = mode 0 on rows normalised by the caller
+        xn = torch.from_numpy(x).double()
+        yn = torch.from_numpy(y).double()
+        xn, yn = xn / (xn.norm(dim=1, keepdim=True) + 1e-20), yn / (yn.norm(dim=1, keepdim=True) + 1e-20)
+        l2, p2 = R.sinkhorn_ref(xn, yn, 1.0, L, 2)
+        assert abs(float(l2) - float(loss)) <= 1e-13 and float((p2 - plan).abs().max()) <= 1e-15
+    assert abs(float(plan.sum(0).sum()) - 1.0) <= 1e-12           # columns marginals 1/S after the last b update
+    # the differentiable form returns the same value
+    lt = R.sinkhorn_detached_plan_loss(torch.from_numpy(x).double()[None], torch.from_numpy(y).double()[None], 1.0, L,
+                                       "l2" if mode else "cosine")
+    assert abs(float(lt[0]) - float(loss)) <= 1e-13
+
+
+@pytest.mark.parametrize("layout", ["stacked", "one_launch_view"])
+def test_meta_stats_ref_equals_the_tensor_formulation(layout):
+    """intertwiner.meta_loss's tensor path on the CPU, in float64, over three steps (the second without small-object
+    statistics): history, counts, the l2 loss from SMALL / BIG / on, and the gradient into the small class features
+    (meta_stats_bwd_ref of the loss's gradient with respect to SMALL)."""
+    from types import SimpleNamespace as NS
+    from helpers import golden_meta_inputs
+    from feature_intertwiner_amd import intertwiner as IT
+    K, F_ = 9, 21
+    G, S = (2, 3) if layout == "stacked" else (1, 3)
+    cfg = NS(DEV=NS(LOSS_CHOICE="l2", INST_LOSS=False))
+    buf = IT.FeatureBuffer(1, F_, K, "cpu")
+    buf.buffer, buf.buffer_cnt = buf.buffer.double(), buf.buffer_cnt.double()
+    seen = []
+    for step in (0, 2, 1):
+        bf, bc, sf, sc = [torch.from_numpy(a).double() for a in golden_meta_inputs(step, K, F_, G=G, activation="sigmoid")]
+        if layout == "one_launch_view":
+            view = lambda t: t[0].permute(1, 0, 2).reshape(F_, S * K).contiguous().view(F_, S, K).permute(1, 0, 2).unsqueeze(0)
+            bf, sf = view(bf), view(sf)
+        old = (buf.buffer[0].clone(), buf.buffer_cnt.reshape(-1).clone())
+        ref = R.meta_stats_ref(bf, bc, sf, sc, *old)
+        sf = sf.detach().requires_grad_(True)
+        loss = IT.meta_loss(cfg, buf, None, [bf, bc, sf, sc, None, None])
+        loss.backward()
+        seen.append(ref["active"])
+        _close(ref["buffer"], buf.buffer[0])
+        assert torch.equal(ref["buffer_cnt"], buf.buffer_cnt.reshape(-1))
+        if not ref["active"]:
+            assert torch.equal(ref["buffer"], old[0]) and float(loss) == 0.0
+            continue
+        SM = ref["SMALL"].clone().requires_grad_(True)
+        on = ref["on"]
+        exp = ((((SM - ref["BIG"]) ** 2).mean(1)) * on).sum() / on.sum().clamp(min=1)
+        assert float(on.sum()) > 0 and abs(float(exp) - float(loss)) <= 1e-13 * abs(float(loss))
+        exp.backward()
+        _close(R.meta_stats_bwd_ref(SM.grad, ref["s_cnt"], sc), sf.grad)
+        assert float(R.meta_stats_bwd_ref(SM.grad, ref["s_cnt"], sc)[..., 0].abs().max()) == 0
+    assert seen == [True, False, True]

@@ -92,16 +92,16 @@ CHECKED_ELSEWHERE = {
     "fi_roi_pool_forward": "tests/test_gpu_roipool.py::test_forward_exact",
     "fi_roi_pool_backward": "tests/test_gpu_roipool.py::test_backward_vs_oracle",
     "fi_nms_sorted": "tests/test_gpu_nms.py::test_pth_nms_matches_oracle",
-    "fi_sinkhorn_forward": "tests/test_gpu_ot.py::test_sinkhorn_vs_oracle",
-    "fi_class_mean_forward": "tests/test_gpu_class_mean.py::test_class_mean_vs_oracle",
-    "fi_class_mean_backward": "tests/test_gpu_class_mean.py::test_class_mean_vs_oracle",
-    "fi_detector_losses": "tests/test_gpu_targets.py::test_detector_losses_kernel_matches_the_loss_functions",
+    "fi_sinkhorn_forward": "tests/test_gpu_loss_kernels.py::test_sinkhorn_forward_matches_fp64",
+    "fi_class_mean_forward": "tests/test_gpu_loss_kernels.py::test_class_mean_matches_fp64",
+    "fi_class_mean_backward": "tests/test_gpu_loss_kernels.py::test_class_mean_matches_fp64",
+    "fi_detector_losses": "tests/test_gpu_loss_kernels.py::test_detector_losses_match_fp64_at_the_edge_shapes",
     "fi_rpn_targets": "tests/test_gpu_targets.py::test_rpn_target_kernels_equal_the_tensor_formulation",
     "fi_detection_targets": "tests/test_gpu_targets.py::test_detection_target_kernel_equals_the_tensor_formulation",
-    "fi_meta_stats_forward": "tests/test_gpu_meta.py::test_statistics_kernels_equal_the_tensor_formulation",
-    "fi_meta_stats_backward": "tests/test_gpu_meta.py::test_statistics_kernels_equal_the_tensor_formulation",
-    "fi_meta_stats_sums": "tests/test_gpu_meta.py::test_meta_loss_split_over_two_ranks_equals_the_reference_goldens",
-    "fi_meta_stats_from_sums": "tests/test_gpu_meta.py::test_meta_loss_split_over_two_ranks_equals_the_reference_goldens",
+    "fi_meta_stats_forward": "tests/test_gpu_loss_kernels.py::test_meta_stats_match_fp64",
+    "fi_meta_stats_backward": "tests/test_gpu_loss_kernels.py::test_meta_stats_match_fp64",
+    "fi_meta_stats_sums": "tests/test_gpu_loss_kernels.py::test_meta_stats_match_fp64",
+    "fi_meta_stats_from_sums": "tests/test_gpu_loss_kernels.py::test_meta_stats_match_fp64",
     "fi_dev_stage_index": "tests/test_gpu_static_dev.py::test_index_kernel_equals_its_tensor_formulation",
     "fi_proposal_candidates": "tests/test_gpu_detector.py::test_proposal_candidates_edge_cases",
     "fi_proposal_candidates_ws": "tests/test_gpu_detector.py::test_proposal_candidates_edge_cases",
