@@ -89,8 +89,10 @@ SIGNATURES = {
     "fi_conv1x1_forward_f16w": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
     "fi_gemm_nt_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "fi_gemm_nt": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "fi_conv2d_forward_live_bf16": (c_int, [c_void_p] * 7 + [c_int] * 16 + [c_void_p, c_void_p]),
-    "fi_conv2d_forward_live_f16": (c_int, [c_void_p] * 7 + [c_int] * 16 + [c_void_p, c_void_p]),
+    "fi_conv2d_forward_live_bf16": (c_int, [c_void_p] * 8 + [c_int] * 16 + [c_void_p, c_void_p]),
+    "fi_conv2d_forward_live_f16": (c_int, [c_void_p] * 8 + [c_int] * 16 + [c_void_p, c_void_p]),
+    "fi_conv2d_forward_plan_bf16": (c_int, [c_void_p] * 8 + [c_int] * 16 + [_ip]),
+    "fi_conv2d_forward_plan_f16": (c_int, [c_void_p] * 8 + [c_int] * 16 + [_ip]),
     "fi_conv2d_weight_grad_rows_bf16": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 12 + [c_void_p, c_void_p]),
     "fi_conv2d_weight_grad_rows_f16": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 12 + [c_void_p, c_void_p]),
     "fi_gemm_nt_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
@@ -168,6 +170,11 @@ for _i, _bm in enumerate((64, 128)):
 
 KERNEL_KEYS = {v: k for k, v in KERNEL_IDS.items()}      # id -> key: what the fi_*_plan queries answer with
 
+# FI_CONV16_* of include/fi_capi.h, by value: what fi_conv2d_forward_plan_{bf16,f16} answer with, and the variants that
+# read the 16-bit weight copy
+CONV16_VARIANTS = ("GENERIC_BM64", "GENERIC_BM128", "PATCH", "PATCH_W16", "PATCH_FLAT_W16", "REG1X1_W16")
+CONV16_READS_COPY = frozenset(i for i, v in enumerate(CONV16_VARIANTS) if v.endswith("_W16"))
+
 
 def kernel_name(key):
     return load().fi_prof_kernel_name(KERNEL_IDS[key]).decode()
@@ -179,6 +186,14 @@ def planned_kernel(query, *args):
     k = ctypes.c_int(-1)
     check(query(*args, ctypes.byref(k)), "kernel plan query")
     return KERNEL_KEYS[k.value]
+
+
+def conv16_variant(query, *args):
+    """Index into CONV16_VARIANTS of the kernel fi_conv2d_forward_live_{bf16,f16} runs: `query` is the matching
+    fi_conv2d_forward_plan_* entry, `args` the launch's arguments up to output_layout."""
+    v = ctypes.c_int(-1)
+    check(query(*args, ctypes.byref(v)), "fi_conv2d_forward_plan (16-bit)")
+    return v.value
 
 _lib = None
 

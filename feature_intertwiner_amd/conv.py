@@ -52,9 +52,9 @@ def conv_precision():
 _LOWP = {"bf16": ("bf16", torch.bfloat16), "fp16": ("f16", torch.float16)}     # precision -> (entry-point suffix, dtype)
 
 
-def _lowp_fn(L, stem, precision, tail=""):
-    """fi_<stem>_{bf16,f16}<tail> of the loaded library."""
-    return getattr(L, "fi_%s_%s%s" % (stem, _LOWP[precision][0], tail))
+def _lowp_fn(L, stem, precision):
+    """fi_<stem>_{bf16,f16} of the loaded library."""
+    return getattr(L, "fi_%s_%s" % (stem, _LOWP[precision][0]))
 
 
 def _log_shape(x, w, stride, padding):
@@ -127,35 +127,6 @@ def _conv_fwd(x, w, b, stride, padding, relu=False, scale=None, residual=None, o
         assert not out_channels_last and gate.shape == y.shape and gate.is_contiguous()
     if bf16:
         _log_flops("conv_bf16_fwd", flops)
-        # 3x3 / stride 1 / pad 1 on maps whose width is a multiple of 16 (or 14-wide RoI maps): patch kernel with the
-        # weights converted to bf16 once per step (cached like W^T) instead of inside every workgroup
-        mt = (Cout + 127) // 128
-        tiled = W % 4 == 0 and W >= 16 and ((N * H + 7) // 8) * ((W + 15) // 16) * mt >= 192
-        # flat 128-pixel tiles for the 14 x 14 RoI maps (even widths below 16)
-        flat = W % 16 != 0 and W < 16 and W % 2 == 0 and (W + 126) // W + 2 <= 13 and \
-            ((N * H * W + 127) // 128) * mt >= 512
-        if (R, S) == (3, 3) and tuple(stride) == (1, 1) and tuple(padding) == (1, 1) and (OH, OW) == (H, W) and \
-                (tiled or flat) and Cout > 64 and not out_channels_last and out_hw is None and \
-                (residual is None or residual.data_ptr() % 16 == 0) and (gate is None or gate.data_ptr() % 16 == 0):
-            wb = _cached_bf16(w, _LOWP[prec][1])
-            with torch.cuda.device(x.device):
-                _lib.check(_lowp_fn(L, "conv3x3_forward_gated", prec, "w")(_lib.ptr(x), _lib.ptr(wb), _lib.ptr(b), _lib.ptr(scale),
-                                                      _lib.ptr(residual), _lib.ptr(gate), _lib.ptr(y), N, Cin, H, W, Cout,
-                                                      1 if relu else 0, 1 if layout == 2 else 0, _lib.current_stream()),
-                           "fi_conv3x3_forward_bf16w")
-            return y
-        # 1x1 / stride 1 with whole quads and 64-channel stages: weights-in-registers kernel, bf16 weights cached
-        if (R, S) == (1, 1) and tuple(stride) == (1, 1) and tuple(padding) == (0, 0) and (H * W) % 4 == 0 and \
-                Cin % 64 == 0 and Cout > 64 and not out_channels_last and out_hw is None and \
-                ((N * H * W + 127) // 128) * ((Cout + 127) // 128) >= 192 and \
-                (residual is None or residual.data_ptr() % 16 == 0) and (gate is None or gate.data_ptr() % 16 == 0):
-            wb = _cached_bf16(w, _LOWP[prec][1])
-            with torch.cuda.device(x.device):
-                _lib.check(_lowp_fn(L, "conv1x1_forward_gated", prec, "w")(_lib.ptr(x), _lib.ptr(wb), _lib.ptr(b), _lib.ptr(scale),
-                                                      _lib.ptr(residual), _lib.ptr(gate), _lib.ptr(y), N, Cin, H * W, Cout,
-                                                      1 if relu else 0, _lib.current_stream()),
-                           "fi_conv1x1_forward_bf16w")
-            return y
     if RING_1X1 and not bf16 and layout >= 1 and R * S == 1 and live is None and out_hw is None and not out_channels_last and _WF:
         e = _WF.get(w.data_ptr())
         if e is not None and e[3]() is not None and e[2] == (Cout, Cin) and (e[1] is None or e[1] == w._version) and \
@@ -170,7 +141,16 @@ def _conv_fwd(x, w, b, stride, padding, relu=False, scale=None, residual=None, o
                 _lib.ptr(live), _lib.current_stream())
         if FLOP_LOG is not None and not bf16:
             _log_flops(_lib.planned_kernel(L.fi_conv2d_forward_plan, *args[:-2]), flops)
-        fn = _lowp_fn(L, "conv2d_forward_live", prec) if bf16 else L.fi_conv2d_forward_live
+        fn = L.fi_conv2d_forward_live
+        if bf16:
+            # the 16-bit copy of the weight goes along: this step's (_prepare_step makes one of every model weight and W^T),
+            # and for a temporary one made here -- only where the library's planner says the launch would read it
+            fn, dtype = _lowp_fn(L, "conv2d_forward_live", prec), _LOWP[prec][1]
+            wb = _cached_bf16(w, dtype, make=False)
+            if wb is None and _lib.conv16_variant(_lowp_fn(L, "conv2d_forward_plan", prec), *args[:2], 16,
+                                                  *args[2:-2]) in _lib.CONV16_READS_COPY:
+                wb = _cached_bf16(w, dtype)
+            args = args[:2] + (_lib.ptr(wb),) + args[2:]
         _lib.check(fn(*args), "fi_conv2d_forward_live")
     return y
 
@@ -824,14 +804,16 @@ _PLAN = weakref.WeakKeyDictionary()      # model -> cached layer lists / descrip
 _WB = {}           # tap-major fp32 weight data_ptr -> (bf16 copy, version, shape): refreshed once per step
 
 
-def _cached_bf16(w, dtype=torch.bfloat16):
+def _cached_bf16(w, dtype=torch.bfloat16, make=True):
     """16-bit copy of a (contiguous, tap-major) fp32 weight, made once per (tensor, version).  Model weights and
     their W^T are converted for ALL layers by one multi-tensor copy per step (_prepare_step fills the cache); anything
-    else (temporaries) is converted here.  The entry keeps `w` alive, so its address cannot be handed to another
-    tensor while the entry exists."""
+    else (temporaries) is converted here -- or, with make=False, left alone: None.  The entry keeps `w` alive, so its
+    address cannot be handed to another tensor while the entry exists."""
     e = _WB.get(w.data_ptr())
     if e is not None and e[1] == w._version and e[0].numel() == w.numel() and e[0].dtype == dtype:
         return e[0].view(w.shape) if e[0].shape != w.shape else e[0]
+    if not make:
+        return None
     wb = w.to(dtype)
     _WB[w.data_ptr()] = (wb, w._version, tuple(w.shape), w)
     return wb

@@ -495,11 +495,11 @@ __global__ __launch_bounds__(kThreads, 2) void conv_bf16_fwd_kernel(const float 
 constexpr int PB_TH = 8, PB_TW = 16;
 constexpr int PB_RP = 28;                       // slots per patch row (24 used)
 constexpr int PB_ROWS = PB_TH + 2;
-constexpr int PB_NSLOT = (PB_ROWS + 1) * PB_RP; // + one row of zeros
 // FLAT tiles (maps of 12..16 columns, e.g. the 14 x 14 RoI maps -- see conv3x3_patch_kernel<true> in conv_igemm.hip):
-// a tile is 128 CONSECUTIVE pixels of the flattened (stacked row, column) space; up to 11 rows + halo
+// a tile is 128 CONSECUTIVE pixels of the flattened (stacked row, column) space; up to 11 rows + halo on 14-wide maps.
+// On 12-wide maps a tile that starts at column 8 ends 11 rows further down: 12 rows + halo, the kernel's FROWS = 14
 constexpr int PB_ROWS_FLAT = 13;
-constexpr int PB_NSLOT_FLAT = (PB_ROWS_FLAT + 1) * PB_RP;
+constexpr int PB_ROWS_FLAT_MAX = 14;
 constexpr int PB_CB = 32;                       // channels per stage = 4 groups of 8
 
 // staging loads of threads whose patch group lies outside the image are redirected here (no branch around the loads)
@@ -521,13 +521,14 @@ __device__ __forceinline__ bf16x8 pack8(const f32x4 &lo, const f32x4 &hi)
 // WB16: the weights are already bf16 (pre-converted once per step by the caller): a lane's A-operand is ONE 16-byte
 // load per (tap, k-step), no packing.  With fp32 weights every wavefront streams 37 KB of weights per 32 channels
 // from L2 -- 8 wavefronts of a CU ask for more than the L2->L1 path delivers at the bf16 MFMA rate.
-template <bool WB16, bool FLAT = false>
+template <bool WB16, bool FLAT = false, int FROWS = PB_ROWS_FLAT>
 __global__ __launch_bounds__(kThreads, 2) void conv3x3_patch_bf16_kernel(const float *__restrict__ x,
                                                                         const void *__restrict__ wv, Epi ep,
                                                                         float *__restrict__ y, PatchGeomB g)
 {
-    constexpr int ROWS = FLAT ? PB_ROWS_FLAT : PB_ROWS;
-    constexpr int NSLOT = FLAT ? PB_NSLOT_FLAT : PB_NSLOT;
+    constexpr int ROWS = FLAT ? FROWS : PB_ROWS;           // flat: the patch rows a tile of this map width can touch
+    constexpr int NSLOT = (ROWS + 1) * PB_RP;              // + one row of zeros
+    static_assert((PB_CB / 8) * ROWS * (FLAT ? 4 : 6) <= kThreads, "one staging item per thread");
     constexpr int SGRP = FLAT ? 4 : 6;            // staged 4-column groups per patch row (flat: columns 0..15 only)
     const float *__restrict__ w = static_cast<const float *>(wv);
     const E16 *__restrict__ wb = static_cast<const E16 *>(wv);
@@ -1639,6 +1640,164 @@ int make_geom(Geom &g, int N, int Cin, int H, int W, int Cout, int R, int S, int
     return FI_OK;
 }
 
+
+// -------------------------------------------------------------------------------------
+// Kernel selection of the forward path (as plan_forward does for the fp32 kernels in conv_igemm.hip).  plan_forward16
+// validates the arguments and decides which kernel a call runs -- host arithmetic on sizes, layouts and pointer VALUES,
+// no HIP call --, fi_conv2d_forward_live_<p> launches exactly what the plan says, and fi_conv2d_forward_plan_<p> runs
+// the same planner for callers that need the answer without a launch (conv._conv_fwd: is a 16-bit weight copy worth
+// making).  The shape and alignment rules of the kernels are the predicates below; the planner and the "run this
+// kernel" entries fi_conv3x3_forward*_<p>w / fi_conv1x1_forward*_<p>w both ask them.
+// -------------------------------------------------------------------------------------
+enum PatchTiling { PT_NONE, PT_TILED, PT_FLAT };
+
+// Patch rows (halo included) that a flat tile of a W-wide map can touch: 128 consecutive pixels, from the last column of
+// a row at worst
+int flat_rows(int W) { return (W + 126) / W + 3; }
+
+// Pixel tiling of conv3x3_patch_bf16_kernel for a map W columns wide.  2-D 8 x 16 tiles: width a multiple of 4, at
+// least 16 (a width that is not a multiple of 16 leaves the last column tile partly empty).  Flat 128-pixel tiles: even
+// widths 12..14 (the 14 x 14 RoI maps), whose tile spans at most PB_ROWS_FLAT_MAX patch rows.
+PatchTiling patch_tiling(int W, int Cin, int Cout)
+{
+    if (Cin % PB_CB != 0 || Cout <= 64) return PT_NONE;
+    if (W % 4 == 0 && W >= PB_TW) return PT_TILED;
+    if (W < PB_TW && W % 2 == 0 && flat_rows(W) <= PB_ROWS_FLAT_MAX) return PT_FLAT;
+    return PT_NONE;
+}
+
+// conv1x1_bf16_kernel: whole quads of pixels per image, whole 64-channel stages
+bool reg1x1_shape(int HW, int Cin, int Cout) { return HW % 4 == 0 && Cin % P1_KC == 0 && Cout > 64; }
+
+// the 16-byte loads and stores of the patch / 1x1 kernels (residual, gate: where given)
+bool aligned16(const void *x, const void *y, const void *residual, const void *gate)
+{
+    return (uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0 && (uintptr_t)residual % 16 == 0 && (uintptr_t)gate % 16 == 0;
+}
+
+// ... and their 32-bit element offsets
+bool fits_int32(int N, int Cin, int Cout, long HW)
+{
+    return (long)N * Cin * HW < 2147483647L && (long)N * Cout * HW < 2147483647L;
+}
+
+// enough 128 x 128 workgroup tiles to fill the chip: below, the generic kernel's finer tiles measured faster
+bool fills_chip(long tiles, bool flat) { return tiles >= (flat ? 512 : 192); }
+
+PatchGeomB patch_geom(PatchTiling t, int N, int Cin, int H, int W, int Cout, int flip)
+{
+    PatchGeomB pg;
+    pg.N = N; pg.Cin = Cin; pg.H = H; pg.W = W; pg.Cout = Cout;
+    pg.flip = flip;
+    pg.tiles_x = t == PT_FLAT ? 1 : fi::ceil_div(W, PB_TW);
+    pg.ptiles = t == PT_FLAT ? fi::ceil_div(N * H * W, 128) : fi::ceil_div(N * H, PB_TH) * pg.tiles_x;
+    pg.mtiles = fi::ceil_div(Cout, 128);
+    return pg;
+}
+
+Conv1x1GeomB reg1x1_geom(int N, int Cin, int HW, int Cout)
+{
+    Conv1x1GeomB pg;
+    pg.N = N; pg.Cin = Cin; pg.HW = HW; pg.Cout = Cout; pg.P = N * HW;
+    pg.ptiles = fi::ceil_div(pg.P, 128);
+    pg.mtiles = fi::ceil_div(Cout, 128);
+    return pg;
+}
+
+struct FwdPlan16 {
+    int variant;           // FI_CONV16_*
+    int mtiles, ptiles;    // generic variants: the tile grid
+    long grid;
+};
+
+// fi_conv2d_forward_live_<p>'s arguments (without the live count and the stream) -> g (all but n_live) and the plan
+int plan_forward16(Geom &g, FwdPlan16 &p, const float *x, const float *weight, const uint16_t *weight16,
+                   const float *residual, const float *gate, const float *y, int N, int Cin, int H, int W, int Cout, int R,
+                   int S, int stride_h, int stride_w, int pad_h, int pad_w, int weight_layout, int out_h, int out_w,
+                   int output_layout)
+{
+    int rc = make_geom(g, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w, out_h, out_w);
+    if (rc != FI_OK) return rc;
+    FI_REQUIRE(x && weight && y, "null pointer");
+    if (Cin % TK != 0 || !(weight_layout == 1 || weight_layout == 2 || R * S == 1)) {
+        fi::set_error("the bf16 path needs Cin %% 32 == 0 and tap-major weights (got Cin = %d, layout %d)", Cin,
+                      weight_layout);
+        return FI_ERR_UNSUPPORTED;
+    }
+    FI_REQUIRE(output_layout == 0 || (Cout % 4 == 0 && residual == nullptr && gate == nullptr && (uintptr_t)y % 16 == 0),
+               "channels-last output needs Cout % 4 == 0, a 16-byte aligned y and no fused residual / gate");
+    FI_REQUIRE(((uintptr_t)weight % 16) == 0, "weights must be 16-byte aligned");
+    FI_REQUIRE(((uintptr_t)weight16 % 16) == 0, "the 16-bit weight copy must be 16-byte aligned");
+    g.flip = weight_layout == 2;
+    g.out_nhwc = output_layout == 1;
+    // what the patch and 1x1 kernels have in common: stride 1, tap-major weights, NCHW output, aligned tensors
+    const bool fast = stride_h == 1 && stride_w == 1 && weight_layout >= 1 && !g.out_nhwc && aligned16(x, y, residual, gate);
+    const bool w16 = fast && weight16 != nullptr && out_h == 0 && out_w == 0 && output_layout == 0;
+    // 3x3 / pad 1 with the output as large as the input: input patch in LDS
+    if (fast && R == 3 && S == 3 && pad_h == 1 && pad_w == 1 && g.OH == H && g.OW == W && !getenv("FI_NO_PATCH") &&
+        fits_int32(N, Cin, Cout, (long)H * W)) {
+        const PatchTiling t = patch_tiling(W, Cin, Cout);
+        // fp32 weights converted inside the kernel: the 2-D tiles only
+        if (t != PT_NONE && (w16 || t == PT_TILED)) {
+            const PatchGeomB pg = patch_geom(t, N, Cin, H, W, Cout, g.flip);
+            if (fills_chip((long)pg.ptiles * pg.mtiles, t == PT_FLAT)) {
+                p.variant = !w16 ? FI_CONV16_PATCH : (t == PT_FLAT ? FI_CONV16_PATCH_FLAT_W16 : FI_CONV16_PATCH_W16);
+                return FI_OK;
+            }
+        }
+    }
+    // 1x1 / pad 0: weights in registers, read from the 16-bit copy
+    if (w16 && R == 1 && S == 1 && pad_h == 0 && pad_w == 0 && reg1x1_shape(H * W, Cin, Cout) &&
+        fits_int32(N, Cin, Cout, (long)H * W)) {
+        const Conv1x1GeomB pg = reg1x1_geom(N, Cin, H * W, Cout);
+        if (fills_chip((long)pg.ptiles * pg.mtiles, false)) {
+            p.variant = FI_CONV16_REG1X1_W16;
+            return FI_OK;
+        }
+    }
+    const long pv = (long)g.N * g.OH * ((g.OW + 3) / 4) * 4;          // virtual pixel space (rows padded to quads)
+    FI_REQUIRE(pv < 2147483647L, "too many output pixels");
+    p.ptiles = fi::ceil_div((int)pv, TN);
+    // 64-row tiles for narrow layers and for grids that would leave CUs idle (C5 at batch 4: 128 workgroups)
+    const int bm = (Cout <= 64 || (long)fi::ceil_div(Cout, 128) * p.ptiles < 512) ? 64 : 128;
+    p.variant = bm == 64 ? FI_CONV16_GENERIC_BM64 : FI_CONV16_GENERIC_BM128;
+    p.mtiles = fi::ceil_div(Cout, bm);
+    p.grid = (long)p.mtiles * fi::ceil_div(p.ptiles, 8) * 8;
+    FI_REQUIRE(p.grid < 2147483647L, "grid too large");
+    return FI_OK;
+}
+
+// conv3x3_patch_bf16_kernel<w16, t == PT_FLAT>; w: fp32 tap-major weights, or their 16-bit copy (w16)
+int launch_patch(bool w16, PatchTiling t, const float *x, const void *w, const Epi &ep, float *y, int N, int Cin, int H,
+                 int W, int Cout, int flip, hipStream_t st)
+{
+    const PatchGeomB pg = patch_geom(t, N, Cin, H, W, Cout, flip);
+    const long blocks = (long)fi::ceil_div(pg.ptiles, 8) * 8 * pg.mtiles;
+    FI_REQUIRE(blocks < 2147483647L, "grid too large");
+    fi::ProfScope prof(FI_K_CONV_BF16_FWD, st);
+    // flat: the 13-row kernel where it covers the map's tiles (14-wide maps), the 14-row one otherwise (12-wide)
+    auto k = !w16 ? conv3x3_patch_bf16_kernel<false>
+                  : (t != PT_FLAT ? conv3x3_patch_bf16_kernel<true, false>
+                                  : (flat_rows(W) <= PB_ROWS_FLAT ? conv3x3_patch_bf16_kernel<true, true>
+                                                                  : conv3x3_patch_bf16_kernel<true, true, PB_ROWS_FLAT_MAX>));
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(kThreads), 0, st, x, w, ep, y, pg);
+    FI_HIP_CHECK(hipGetLastError());
+    return FI_OK;
+}
+
+int launch_reg1x1(const float *x, const uint16_t *w16, const Epi &ep, float *y, int N, int Cin, int HW, int Cout,
+                  hipStream_t st)
+{
+    const Conv1x1GeomB pg = reg1x1_geom(N, Cin, HW, Cout);
+    const long blocks = (long)fi::ceil_div(pg.ptiles, 8) * 8 * pg.mtiles;
+    FI_REQUIRE(blocks < 2147483647L, "grid too large");
+    fi::ProfScope prof(FI_K_CONV_BF16_FWD, st);
+    hipLaunchKernelGGL(conv1x1_bf16_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, x,
+                       reinterpret_cast<const E16 *>(w16), ep, y, pg);
+    FI_HIP_CHECK(hipGetLastError());
+    return FI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1658,69 +1817,59 @@ int FI16(fi_conv2d_forward_gated, )(const float *x, const float *weight, const f
                                  int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int relu,
                                  int weight_layout, int out_h, int out_w, int output_layout, fi_stream_t stream)
 {
-    return FI16(fi_conv2d_forward_live, )(x, weight, bias, scale, residual, gate, y, N, Cin, H, W, Cout, R, S, stride_h,
-                                          stride_w, pad_h, pad_w, relu, weight_layout, out_h, out_w, output_layout, nullptr,
-                                          stream);
+    return FI16(fi_conv2d_forward_live, )(x, weight, nullptr, bias, scale, residual, gate, y, N, Cin, H, W, Cout, R, S,
+                                          stride_h, stride_w, pad_h, pad_w, relu, weight_layout, out_h, out_w, output_layout,
+                                          nullptr, stream);
 }
 
-int FI16(fi_conv2d_forward_live, )(const float *x, const float *weight, const float *bias, const float *scale,
-                                const float *residual, const float *gate, float *y, int N, int Cin, int H, int W,
-                                int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int relu,
-                                int weight_layout, int out_h, int out_w, int output_layout, const int32_t *n_live_dev,
-                                fi_stream_t stream)
+int FI16(fi_conv2d_forward_live, )(const float *x, const float *weight, const uint16_t *weight16, const float *bias,
+                                const float *scale, const float *residual, const float *gate, float *y, int N, int Cin,
+                                int H, int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
+                                int relu, int weight_layout, int out_h, int out_w, int output_layout,
+                                const int32_t *n_live_dev, fi_stream_t stream)
 {
     Geom g;
-    int rc = make_geom(g, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w, out_h, out_w);
+    FwdPlan16 plan;
+    const int rc = plan_forward16(g, plan, x, weight, weight16, residual, gate, y, N, Cin, H, W, Cout, R, S, stride_h,
+                                  stride_w, pad_h, pad_w, weight_layout, out_h, out_w, output_layout);
     if (rc != FI_OK) return rc;
-    FI_REQUIRE(x && weight && y, "null pointer");
-    if (Cin % TK != 0 || !(weight_layout == 1 || weight_layout == 2 || R * S == 1)) {
-        fi::set_error("the bf16 path needs Cin %% 32 == 0 and tap-major weights (got Cin = %d, layout %d)", Cin,
-                      weight_layout);
-        return FI_ERR_UNSUPPORTED;
-    }
-    FI_REQUIRE(output_layout == 0 || (Cout % 4 == 0 && residual == nullptr && gate == nullptr && (uintptr_t)y % 16 == 0),
-               "channels-last output needs Cout % 4 == 0, a 16-byte aligned y and no fused residual / gate");
-    FI_REQUIRE(((uintptr_t)weight % 16) == 0, "weights must be 16-byte aligned");
-    g.flip = weight_layout == 2;
-    g.out_nhwc = output_layout == 1;
-    g.n_live = n_live_dev;               // honoured by conv_bf16_fwd_kernel; the patch kernel computes every image
+    g.n_live = n_live_dev;               // honoured by conv_bf16_fwd_kernel; the patch / 1x1 kernels compute every image
     const Epi ep = {bias, scale, residual, relu, gate};
     hipStream_t st = (hipStream_t)stream;
-    // 3x3 / stride 1 / pad 1 on maps at least 16 columns wide (whole 4-column groups): input patch in LDS
-    if (!getenv("FI_NO_PATCH") && R == 3 && S == 3 && stride_h == 1 && stride_w == 1 && pad_h == 1 && pad_w == 1 &&
-        g.OH == H && g.OW == W && W % 4 == 0 && W >= PB_TW && !g.out_nhwc && Cout > 64 && weight_layout >= 1 &&
-        (uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0 && (residual == nullptr || (uintptr_t)residual % 16 == 0) &&
-        (gate == nullptr || (uintptr_t)gate % 16 == 0) && (long)N * Cin * H * W < 2147483647L && (long)N * Cout * H * W < 2147483647L) {
-        PatchGeomB pg;
-        pg.N = N; pg.Cin = Cin; pg.H = H; pg.W = W; pg.Cout = Cout;
-        pg.flip = g.flip;
-        pg.tiles_x = fi::ceil_div(W, PB_TW);                 // W % 16 != 0: the last column tile is partly empty
-        pg.ptiles = fi::ceil_div(N * H, PB_TH) * pg.tiles_x;
-        pg.mtiles = fi::ceil_div(Cout, 128);
-        if ((long)pg.ptiles * pg.mtiles >= 192) {
-            const long blocks = (long)fi::ceil_div(pg.ptiles, 8) * 8 * pg.mtiles;
-            fi::ProfScope prof(FI_K_CONV_BF16_FWD, st);
-            hipLaunchKernelGGL(conv3x3_patch_bf16_kernel<false>, dim3((unsigned)blocks), dim3(kThreads), 0, st, x,
-                               static_cast<const void *>(weight), ep, y, pg);
-            FI_HIP_CHECK(hipGetLastError());
-            return FI_OK;
-        }
+    switch (plan.variant) {
+    case FI_CONV16_PATCH:
+        return launch_patch(false, PT_TILED, x, weight, ep, y, N, Cin, H, W, Cout, g.flip, st);
+    case FI_CONV16_PATCH_W16:
+        return launch_patch(true, PT_TILED, x, weight16, ep, y, N, Cin, H, W, Cout, g.flip, st);
+    case FI_CONV16_PATCH_FLAT_W16:
+        return launch_patch(true, PT_FLAT, x, weight16, ep, y, N, Cin, H, W, Cout, g.flip, st);
+    case FI_CONV16_REG1X1_W16:
+        return launch_reg1x1(x, weight16, ep, y, N, Cin, H * W, Cout, st);
+    default: {
+        fi::ProfScope prof(FI_K_CONV_BF16_FWD, st);
+        const bool s2 = (stride_w == 2 && W >= 8);
+        auto k = plan.variant == FI_CONV16_GENERIC_BM64 ? (s2 ? conv_bf16_fwd_kernel<64, 2> : conv_bf16_fwd_kernel<64, 1>)
+                                                        : (s2 ? conv_bf16_fwd_kernel<128, 2> : conv_bf16_fwd_kernel<128, 1>);
+        hipLaunchKernelGGL(k, dim3((unsigned)plan.grid), dim3(kThreads), 0, st, x, weight, ep, y, g, plan.mtiles,
+                           plan.ptiles);
+        FI_HIP_CHECK(hipGetLastError());
+        return FI_OK;
     }
-    const long pv = (long)g.N * g.OH * ((g.OW + 3) / 4) * 4;          // virtual pixel space (rows padded to quads)
-    FI_REQUIRE(pv < 2147483647L, "too many output pixels");
-    const int ptiles = fi::ceil_div((int)pv, TN);
-    // 64-row tiles for narrow layers and for grids that would leave CUs idle (C5 at batch 4: 128 workgroups)
-    const int bm = (Cout <= 64 || (long)fi::ceil_div(Cout, 128) * ptiles < 512) ? 64 : 128;
-    const int mtiles = fi::ceil_div(Cout, bm);
-    const long grid = (long)mtiles * fi::ceil_div(ptiles, 8) * 8;
-    FI_REQUIRE(grid < 2147483647L, "grid too large");
-    fi::ProfScope prof(FI_K_CONV_BF16_FWD, st);
-    const bool s2 = (stride_w == 2 && W >= 8);
-    auto k = bm == 64 ? (s2 ? conv_bf16_fwd_kernel<64, 2> : conv_bf16_fwd_kernel<64, 1>)
-                      : (s2 ? conv_bf16_fwd_kernel<128, 2> : conv_bf16_fwd_kernel<128, 1>);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kThreads), 0, st, x, weight, ep, y, g, mtiles, ptiles);
-    FI_HIP_CHECK(hipGetLastError());
-    return FI_OK;
+    }
+}
+
+int FI16(fi_conv2d_forward_plan, )(const float *x, const float *weight, const uint16_t *weight16, const float *bias,
+                                const float *scale, const float *residual, const float *gate, float *y, int N, int Cin,
+                                int H, int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
+                                int relu, int weight_layout, int out_h, int out_w, int output_layout, int *variant)
+{
+    FI_REQUIRE(variant != nullptr, "null pointer");
+    Geom g;
+    FwdPlan16 plan;
+    const int rc = plan_forward16(g, plan, x, weight, weight16, residual, gate, y, N, Cin, H, W, Cout, R, S, stride_h,
+                                  stride_w, pad_h, pad_w, weight_layout, out_h, out_w, output_layout);
+    if (rc == FI_OK) *variant = plan.variant;
+    return rc;
 }
 
 int FI16(fi_conv3x3_forward, w)(const float *x, const uint16_t *weight_bf16, const float *bias, const float *scale,
@@ -1737,38 +1886,16 @@ int FI16(fi_conv3x3_forward_gated, w)(const float *x, const uint16_t *weight_bf1
 {
     FI_REQUIRE(N >= 1 && Cin >= 1 && H >= 1 && W >= 1 && Cout >= 1, "sizes must be positive");
     FI_REQUIRE(x && weight_bf16 && y, "null pointer");
-    // 2-D tiles: width a multiple of 4, at least 16 (a width that is not a multiple of 16 leaves the last column tile
-    // partly empty).  Flat tiles: even widths 12..14 (the 14 x 14 RoI maps)
-    const bool tiled = W % 4 == 0 && W >= PB_TW;
-    const bool flat = !tiled && W < 16 && W % 2 == 0 && (W + 126) / W + 2 <= PB_ROWS_FLAT;
-    if (!((tiled || flat) && Cin % PB_CB == 0 && Cout > 64)) {
+    const PatchTiling t = patch_tiling(W, Cin, Cout);
+    if (t == PT_NONE) {
         fi::set_error("fi_conv3x3_forward_bf16w needs W %% 4 == 0 (W %% 16 == 0 for full tiles) and W >= 16, or W in {12, 14}; Cin %% 32 == 0 and Cout > 64 (got W = %d, Cin = %d, Cout = %d)",
                       W, Cin, Cout);
         return FI_ERR_UNSUPPORTED;
     }
-    FI_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0 && (uintptr_t)weight_bf16 % 16 == 0 &&
-               (residual == nullptr || (uintptr_t)residual % 16 == 0) && (gate == nullptr || (uintptr_t)gate % 16 == 0),
-               "16-byte aligned tensors required");
-    FI_REQUIRE((long)N * Cin * H * W < 2147483647L && (long)N * Cout * H * W < 2147483647L, "tensor too large");
-    PatchGeomB pg;
-    pg.N = N; pg.Cin = Cin; pg.H = H; pg.W = W; pg.Cout = Cout;
-    pg.flip = flip_taps ? 1 : 0;
-    pg.tiles_x = flat ? 1 : fi::ceil_div(W, PB_TW);
-    pg.ptiles = flat ? fi::ceil_div(N * H * W, 128) : fi::ceil_div(N * H, PB_TH) * pg.tiles_x;
-    pg.mtiles = fi::ceil_div(Cout, 128);
+    FI_REQUIRE(aligned16(x, y, residual, gate) && (uintptr_t)weight_bf16 % 16 == 0, "16-byte aligned tensors required");
+    FI_REQUIRE(fits_int32(N, Cin, Cout, (long)H * W), "tensor too large");
     const Epi ep = {bias, scale, residual, relu, gate};
-    hipStream_t st = (hipStream_t)stream;
-    const long blocks = (long)fi::ceil_div(pg.ptiles, 8) * 8 * pg.mtiles;
-    FI_REQUIRE(blocks < 2147483647L, "grid too large");
-    fi::ProfScope prof(FI_K_CONV_BF16_FWD, st);
-    if (flat)
-        hipLaunchKernelGGL((conv3x3_patch_bf16_kernel<true, true>), dim3((unsigned)blocks), dim3(kThreads), 0, st, x,
-                           static_cast<const void *>(weight_bf16), ep, y, pg);
-    else
-        hipLaunchKernelGGL((conv3x3_patch_bf16_kernel<true, false>), dim3((unsigned)blocks), dim3(kThreads), 0, st, x,
-                           static_cast<const void *>(weight_bf16), ep, y, pg);
-    FI_HIP_CHECK(hipGetLastError());
-    return FI_OK;
+    return launch_patch(true, t, x, weight_bf16, ep, y, N, Cin, H, W, Cout, flip_taps ? 1 : 0, (hipStream_t)stream);
 }
 
 int FI16(fi_conv1x1_forward, w)(const float *x, const uint16_t *weight_bf16, const float *bias, const float *scale,
@@ -1784,28 +1911,15 @@ int FI16(fi_conv1x1_forward_gated, w)(const float *x, const uint16_t *weight_bf1
 {
     FI_REQUIRE(N >= 1 && Cin >= 1 && HW >= 1 && Cout >= 1, "sizes must be positive");
     FI_REQUIRE(x && weight_bf16 && y, "null pointer");
-    if (!(HW % 4 == 0 && Cin % P1_KC == 0 && Cout > 64)) {
+    if (!reg1x1_shape(HW, Cin, Cout)) {
         fi::set_error("fi_conv1x1_forward_bf16w needs H*W %% 4 == 0, Cin %% 64 == 0 and Cout > 64 (got H*W = %d, Cin = %d, Cout = %d)",
                       HW, Cin, Cout);
         return FI_ERR_UNSUPPORTED;
     }
-    FI_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0 && (uintptr_t)weight_bf16 % 16 == 0 &&
-               (residual == nullptr || (uintptr_t)residual % 16 == 0) && (gate == nullptr || (uintptr_t)gate % 16 == 0),
-               "16-byte aligned tensors required");
-    FI_REQUIRE((long)N * Cin * HW < 2147483647L && (long)N * Cout * HW < 2147483647L, "tensor too large");
-    Conv1x1GeomB pg;
-    pg.N = N; pg.Cin = Cin; pg.HW = HW; pg.Cout = Cout; pg.P = N * HW;
-    pg.ptiles = fi::ceil_div(pg.P, 128);
-    pg.mtiles = fi::ceil_div(Cout, 128);
+    FI_REQUIRE(aligned16(x, y, residual, gate) && (uintptr_t)weight_bf16 % 16 == 0, "16-byte aligned tensors required");
+    FI_REQUIRE(fits_int32(N, Cin, Cout, HW), "tensor too large");
     const Epi ep = {bias, scale, residual, relu, gate};
-    hipStream_t st = (hipStream_t)stream;
-    const long blocks = (long)fi::ceil_div(pg.ptiles, 8) * 8 * pg.mtiles;
-    FI_REQUIRE(blocks < 2147483647L, "grid too large");
-    fi::ProfScope prof(FI_K_CONV_BF16_FWD, st);
-    hipLaunchKernelGGL(conv1x1_bf16_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, x,
-                       reinterpret_cast<const E16 *>(weight_bf16), ep, y, pg);
-    FI_HIP_CHECK(hipGetLastError());
-    return FI_OK;
+    return launch_reg1x1(x, weight_bf16, ep, y, N, Cin, HW, Cout, (hipStream_t)stream);
 }
 
 int FI16(fi_conv2d_weight_grad, )(const float *x, const float *dy, float *dweight, int N, int Cin, int H, int W,

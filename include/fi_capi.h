@@ -538,17 +538,52 @@ int fi_stride2_interleave_gated(const float *c00, const float *c01, const float 
 
 /* The live-count entry points on the 16-bit kernels (see fi_conv2d_forward_live / fi_gemm_nt_rows): the forward of a
  * static-capacity batch, and the weight-gradient kernel used as the GEMM of conv.linear (dweight [Cout = rows][Cin], zero
- * filled by the call unless FI_OUTPUTS_ZEROED) with a device count of live rows. */
-int fi_conv2d_forward_live_bf16(const float *x, const float *weight, const float *bias, const float *scale,
-                                const float *residual, const float *gate, float *y, int N, int Cin, int H, int W,
-                                int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int relu,
-                                int weight_layout, int out_h, int out_w, int output_layout, const int32_t *n_live_dev,
-                                fi_stream_t stream);
-int fi_conv2d_forward_live_f16(const float *x, const float *weight, const float *bias, const float *scale,
-                               const float *residual, const float *gate, float *y, int N, int Cin, int H, int W,
-                               int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int relu,
-                               int weight_layout, int out_h, int out_w, int output_layout, const int32_t *n_live_dev,
-                               fi_stream_t stream);
+ * filled by the call unless FI_OUTPUTS_ZEROED) with a device count of live rows.
+ *
+ * fi_conv2d_forward_live_<p> is THE forward / data-gradient entry of the 16-bit path (fi_conv2d_forward_<p> and _gated_<p>
+ * call it): one host-side planner decides among all of its kernels, and the call launches what the plan says.
+ * weight16: the same weights in the 16-bit type (uint16 bit patterns, same element order as `weight`, 16-byte aligned --
+ * FI_ERR_INVALID_ARG otherwise), or NULL.  Three variants read it INSTEAD of `weight`, so the caller converts once per
+ * step and not every workgroup for itself; all of them need stride 1, weight_layout >= 1, out_h == out_w == 0,
+ * output_layout 0 and 16-byte aligned x, y, residual and gate:
+ *   FI_CONV16_PATCH_W16       3x3 / pad 1, W % 4 == 0 and W >= 16, Cout > 64, at least 192 tiles of 8 x 16 pixels x 128 channels
+ *   FI_CONV16_PATCH_FLAT_W16  3x3 / pad 1, W in {12, 14}, Cout > 64, at least 512 tiles of 128 pixels x 128 channels
+ *   FI_CONV16_REG1X1_W16      1x1 / pad 0, H * W % 4 == 0, Cin % 64 == 0, Cout > 64, at least 192 such tiles
+ * Where none applies (or weight16 is NULL): FI_CONV16_PATCH, the 2-D patch kernel converting the fp32 weights itself, under
+ * the conditions of FI_CONV16_PATCH_W16 but for any out_h / out_w that equal H / W; else the generic kernel on 64- or
+ * 128-row tiles.  n_live_dev does not enter the choice and only the generic kernel honours it.  FI_NO_PATCH in the
+ * environment turns the three patch variants off. */
+enum {
+    FI_CONV16_GENERIC_BM64 = 0,      /* conv_bf16_fwd_kernel<64, *> */
+    FI_CONV16_GENERIC_BM128 = 1,     /* conv_bf16_fwd_kernel<128, *> */
+    FI_CONV16_PATCH = 2,             /* conv3x3_patch_bf16_kernel<false>: fp32 weights, converted in the kernel */
+    FI_CONV16_PATCH_W16 = 3,         /* conv3x3_patch_bf16_kernel<true, false> */
+    FI_CONV16_PATCH_FLAT_W16 = 4,    /* conv3x3_patch_bf16_kernel<true, true> */
+    FI_CONV16_REG1X1_W16 = 5         /* conv1x1_bf16_kernel */
+};
+int fi_conv2d_forward_live_bf16(const float *x, const float *weight, const uint16_t *weight16, const float *bias,
+                                const float *scale, const float *residual, const float *gate, float *y, int N, int Cin,
+                                int H, int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
+                                int relu, int weight_layout, int out_h, int out_w, int output_layout,
+                                const int32_t *n_live_dev, fi_stream_t stream);
+int fi_conv2d_forward_live_f16(const float *x, const float *weight, const uint16_t *weight16, const float *bias,
+                               const float *scale, const float *residual, const float *gate, float *y, int N, int Cin,
+                               int H, int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
+                               int relu, int weight_layout, int out_h, int out_w, int output_layout,
+                               const int32_t *n_live_dev, fi_stream_t stream);
+/* Which variant fi_conv2d_forward_live_<p> runs for these arguments: writes its FI_CONV16_* to *variant.  A host-only query
+ * (no HIP call, nothing launched; pointers are inspected for NULL and alignment, never dereferenced) that runs the planner
+ * and the argument checks of the entry itself: the same status for every argument list.  A caller that has no 16-bit copy
+ * yet may pass any non-NULL 16-byte aligned value as weight16 to ask "would you use one" (conv._conv_fwd does, before it
+ * converts a temporary). */
+int fi_conv2d_forward_plan_bf16(const float *x, const float *weight, const uint16_t *weight16, const float *bias,
+                                const float *scale, const float *residual, const float *gate, float *y, int N, int Cin,
+                                int H, int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
+                                int relu, int weight_layout, int out_h, int out_w, int output_layout, int *variant);
+int fi_conv2d_forward_plan_f16(const float *x, const float *weight, const uint16_t *weight16, const float *bias,
+                               const float *scale, const float *residual, const float *gate, float *y, int N, int Cin,
+                               int H, int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
+                               int relu, int weight_layout, int out_h, int out_w, int output_layout, int *variant);
 int fi_conv2d_weight_grad_rows_bf16(const float *x, const float *dy, float *dweight, int N, int Cin, int H, int W,
                                     int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int flags,
                                     const int32_t *rows_live_dev, fi_stream_t stream);
@@ -663,7 +698,10 @@ int fi_conv2d_forward_bf16(const float *x, const float *weight, const float *bia
                            int H, int W, int Cout, int R, int S, int stride_h, int stride_w,
                            int pad_h, int pad_w, int relu, int weight_layout, int out_h, int out_w,
                            int output_layout, fi_stream_t stream);
-/* 3x3 / stride 1 / pad 1 forward (flip_taps = 0) or data gradient (flip_taps = 1, weight = W^T [Cin][3][3][Cout])
+/* "Run this kernel" entries of the two kernels that read 16-bit weights (fi_conv2d_forward_live_bf16 plans; these take
+ * the kernel as given, whatever the number of tiles, and check its shape and alignment rules with the planner's own
+ * predicates).
+ * 3x3 / stride 1 / pad 1 forward (flip_taps = 0) or data gradient (flip_taps = 1, weight = W^T [Cin][3][3][Cout])
  * with tap-major weights ALREADY in bf16 (uint16 bit patterns, converted once per step by the caller): the input
  * patch of a tile is staged once per 32 channels in LDS, weights go straight into the MFMA operand registers.
  * Needs W % 4 == 0 and W >= 16 (8 x 16 tiles; W % 16 == 0 for full ones) or W in {12, 14} (flat 128-pixel tiles: the

@@ -54,8 +54,10 @@ class Wrapped(object):
 
     def __getattr__(self, name):
         fn = getattr(self._real, name)
-        if not name.startswith("fi_conv") or name.endswith("_eligible"):       # (a host-side query, not a launch)
+        if not name.startswith("fi_conv") or name.endswith("_eligible") or "_plan" in name:   # (host-side queries, not launches)
             return fn
+        # the 16-bit forward entry plans its kernel: label the launch by the variant its own query names
+        query = getattr(self._real, name.replace("_live_", "_plan_")) if name.startswith("fi_conv2d_forward_live_") else None
 
         def timed(*a):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -63,7 +65,8 @@ class Wrapped(object):
             rc = fn(*a)
             e1.record()
             ints = tuple(int(v) if isinstance(v, int) else None for v in a)
-            records.append((name, ints, e0, e1))
+            variant = _lib.CONV16_VARIANTS[_lib.conv16_variant(query, *a[:-2])] if query is not None else None
+            records.append((name, ints, e0, e1, variant))
             return rc
         return timed
 
@@ -78,8 +81,11 @@ live_shares = [sh for tag, sh in _conv.LIVE_LOG if tag == "conv"]
 _conv.FLOP_LOG = _conv.LIVE_LOG = None
 
 
-def describe(name, a):
+def describe(name, a, variant=None):
     v = [x for x in a if x is not None]
+    if variant is not None:
+        key, fl = describe(name, a)
+        return key + " " + variant, fl
     gated = "_gated" in name
     name = name.replace("_gated", "")
     if name.endswith("_live") or "_live_" in name:
@@ -94,12 +100,6 @@ def describe(name, a):
         fl = 2.0 * N * Cout * OH * OW * Cin * R * S
         return "fwd%s N%d %dx%d Cin%d->Cout%d k%dx%d s%d p%d lay%d%s" % (
             "_bf16" if "bf16" in name else "", N, H, W, Cin, Cout, R, S, sh, ph, layout, " cl" if ocl else ""), fl
-    if name in ("fi_conv3x3_forward_bf16w",):
-        N, Cin, H, W, Cout = v[:5]
-        return "fwd_bf16w3x3 N%d %dx%d Cin%d->Cout%d" % (N, H, W, Cin, Cout), 2.0 * N * Cout * H * W * Cin * 9
-    if name in ("fi_conv1x1_forward_bf16w",):
-        N, Cin, HW, Cout = v[:4]
-        return "fwd_bf16w1x1 N%d HW%d Cin%d->Cout%d" % (N, HW, Cin, Cout), 2.0 * N * Cout * HW * Cin
     if name in ("fi_conv2d_weight_grad_batch", "fi_conv2d_weight_grad_batch_bf16", "fi_conv2d_weight_grad_batch_f16"):
         # (x[], dy[], dw[], db[], n, N, Cin, H, W, Cout, R, S, 1, 1, ph, pw, ...) -- the 16-bit entry points take the same
         # arguments (round 5's cfg5 file had this row at 0.0 TFLOP/s: the script did not know the name)
@@ -118,8 +118,8 @@ def describe(name, a):
 
 
 agg = collections.OrderedDict()
-for name, a, e0, e1 in records:
-    key, fl = describe(name, a)
+for name, a, e0, e1, variant in records:
+    key, fl = describe(name, a, variant)
     e = agg.setdefault(key, [0, 0.0, 0.0])
     e[0] += 1
     e[1] += e0.elapsed_time(e1) * 1e3

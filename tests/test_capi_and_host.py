@@ -205,6 +205,87 @@ def test_plan_queries_name_the_kernel_on_both_sides_of_every_threshold():
         assert _planned(L.fi_gemm_nt_plan, *g) == L.fi_gemm_nt_affine(*g, None, None) == -1, g
 
 
+def test_16bit_forward_plan_names_the_variant_on_both_sides_of_every_threshold():
+    """fi_conv2d_forward_plan_{bf16,f16} is the planner of fi_conv2d_forward_live_{bf16,f16} run on the host: aligned fake
+    pointer values, shapes on both sides of every threshold of csrc/conv_bf16.hip (tile counts in the comments: 8 x 16 or
+    128-pixel tiles x 128 output channels), each with and without a 16-bit weight copy.  tests/test_gpu_conv16_plan.py
+    holds the launches of the same shapes to the variant named here."""
+    import ctypes
+    from feature_intertwiner_amd import _lib
+    L = _lib.load()
+    X, Wt, W16, Y, G, RES = 0x10000, 0x20000, 0x30000, 0x40000, 0x50000, 0x60000
+
+    def plan(sfx, N, Cin, H, W, R, stride, pad, copy, Cout=256, x=X, y=Y, residual=None, gate=None, out_hw=(0, 0), ocl=0,
+             w16=W16):
+        v = ctypes.c_int(-1)
+        rc = getattr(L, "fi_conv2d_forward_plan_" + sfx)(x, Wt, w16 if copy else None, None, None, residual, gate, y, N, Cin,
+                                                          H, W, Cout, R, R, stride, stride, pad, pad, 0, 1, out_hw[0],
+                                                          out_hw[1], ocl, ctypes.byref(v))
+        return _lib.CONV16_VARIANTS[v.value] if rc == 0 else rc
+
+    def both(sfx, *a, **kw):
+        return plan(sfx, *a, True, **kw), plan(sfx, *a, False, **kw)
+
+    for sfx in ("bf16", "f16"):
+        c3 = lambda N, H, W, **kw: both(sfx, N, 32, H, W, 3, 1, 1, **kw)              # 3x3 / s1 / p1, Cin 32
+        c1 = lambda N, Cin, H, W, **kw: both(sfx, N, Cin, H, W, 1, 1, 0, **kw)        # 1x1 / s1 / p0
+        # 2-D patch tiles from 192 workgroups
+        assert c3(1, 96, 128) == ("PATCH_W16", "PATCH")                               # 12 x 8 x 2 = 192 tiles
+        assert c3(1, 88, 128) == ("GENERIC_BM64", "GENERIC_BM64")                     # 176
+        assert c3(1, 96, 132) == ("PATCH_W16", "PATCH")                               # 216, the last column tile partial
+        assert c3(1, 96, 130) == ("GENERIC_BM64", "GENERIC_BM64")                     # W % 4 != 0
+        # flat tiles (widths 12 and 14) from 512 workgroups, only with a copy; the generic kernel's 128 rows from 512 of
+        # ITS tiles (rows padded to quads: 14 -> 16 columns)
+        assert c3(167, 14, 14) == ("PATCH_FLAT_W16", "GENERIC_BM128")                 # 256 x 2 = 512 flat; 293 x 2 generic
+        assert c3(166, 14, 14) == ("GENERIC_BM128", "GENERIC_BM128")                  # 510 flat; 291 x 2 generic
+        # (227 x 144 pixels are 256 generic tiles x 2 = 512: 128 rows.  The issue's table says GENERIC_BM64 for this
+        # launch without a copy; the parent commit's bm rule -- `tiles < 512 ? 64 : 128` -- gives 128 rows.)
+        assert c3(227, 12, 12) == ("PATCH_FLAT_W16", "GENERIC_BM128")                 # 512 flat
+        assert c3(226, 12, 12) == ("GENERIC_BM64", "GENERIC_BM64")                    # 510 flat, 510 generic
+        assert c3(400, 10, 10) == ("GENERIC_BM128", "GENERIC_BM128")                  # width 10: 15 patch rows per tile
+        # 16-byte alignment of every tensor the fast kernels touch
+        for kw in (dict(gate=G + 8), dict(residual=RES + 8), dict(x=X + 8), dict(y=Y + 8)):
+            assert c3(167, 14, 14, **kw) == ("GENERIC_BM128", "GENERIC_BM128"), kw
+        # an explicit output size, channels-last output: no variant that reads the copy
+        assert c3(1, 96, 128, out_hw=(96, 128)) == ("PATCH", "PATCH")
+        assert c3(1, 96, 128, ocl=1) == ("GENERIC_BM64", "GENERIC_BM64")
+        # 1x1: weights in registers from 192 tiles, whole 64-channel stages, whole quads, more than 64 output channels
+        assert c1(1, 64, 96, 128) == ("REG1X1_W16", "GENERIC_BM64")                   # 96 x 2 = 192
+        assert c1(1, 64, 95, 128) == ("GENERIC_BM64", "GENERIC_BM64")                 # 190
+        assert c1(1, 96, 96, 128) == ("GENERIC_BM64", "GENERIC_BM64")                 # Cin % 64
+        assert c1(3, 64, 65, 63) == ("GENERIC_BM64", "GENERIC_BM64")                  # H*W % 4
+        assert c1(4, 64, 128, 128) == ("REG1X1_W16", "GENERIC_BM128")                 # 1024 tiles
+        assert c1(1, 64, 96, 128, Cout=64) == ("GENERIC_BM64", "GENERIC_BM64")
+        # generic tile height, 3x3 / s2 / p1
+        assert both(sfx, 1, 32, 512, 256, 3, 2, 1) == ("GENERIC_BM128", "GENERIC_BM128")      # 512
+        assert both(sfx, 1, 32, 508, 256, 3, 2, 1) == ("GENERIC_BM64", "GENERIC_BM64")        # 508
+
+        # an argument the launch entry rejects is rejected by the query, with the same status (and before any HIP call)
+        live = getattr(L, "fi_conv2d_forward_live_" + sfx)
+        query = getattr(L, "fi_conv2d_forward_plan_" + sfx)
+        ok = (1, 32, 96, 128, 256, 3, 3, 1, 1, 1, 1, 0, 1, 0, 0, 0)
+        for ptrs, tail, status in (((X, Wt, W16, None, None, None, None, Y), (1, 48) + ok[2:], -3),      # Cin % 32
+                                   ((None, Wt, W16, None, None, None, None, Y), ok, -1),                 # no x
+                                   ((X, Wt, W16 + 8, None, None, None, None, Y), ok, -1),                # copy misaligned
+                                   ((X, Wt + 8, None, None, None, None, None, Y), ok, -1),               # weight misaligned
+                                   ((X, Wt, None, None, None, None, G, Y), ok[:-1] + (1,), -1),          # gate + channels-last
+                                   ((X, Wt, W16, None, None, None, None, Y), (0,) + ok[1:], -1)):        # empty batch
+            v = ctypes.c_int(-1)
+            assert query(*ptrs, *tail, ctypes.byref(v)) == live(*ptrs, *tail, None, None) == status, (ptrs, tail)
+        assert query(X, Wt, None, None, None, None, None, Y, *ok, None) == -1
+
+
+def test_forward_kernel_selection_of_the_16bit_path_is_stated_once():
+    """The tile sizes and thresholds that choose a 16-bit forward kernel live in csrc/conv_bf16.hip alone: conv._conv_fwd
+    hands the launch entry what it has and restates none of them."""
+    import inspect
+    from feature_intertwiner_amd import conv
+    src = inspect.getsource(conv._conv_fwd)
+    for token in ("192", "512", "126", "% 64", "Cout > 64", "forward_gated"):
+        assert token not in src, token
+    assert "tail" not in inspect.signature(conv._lowp_fn).parameters
+
+
 def test_reference_shaped_python_surface():
     import inspect
     from feature_intertwiner_amd.roi_align.crop_and_resize import CropAndResizeFunction

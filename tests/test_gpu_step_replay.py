@@ -28,7 +28,7 @@ DEV = "cuda:0"
 _XIN = ["N", "Cin", "H", "W", "Cout", "R", "S", "sh", "sw", "ph", "pw"]
 _FWD = _XIN + ["relu", "layout", "oh", "ow", "ocl"]
 # entry point -> (family, argument names in C order); the names in _PTRS are pointers, every other one an integer
-_PTRS = {"x", "w", "bias", "scale", "residual", "gate", "y", "dy", "dw", "dbias", "xs", "dys", "dws", "dbs", "a", "b", "c",
+_PTRS = {"x", "w", "w16", "bias", "scale", "residual", "gate", "y", "dy", "dw", "dbias", "xs", "dys", "dws", "dbs", "a", "b", "c",
          "ws", "live", "stream"}
 SPECS = {
     "fi_conv2d_forward": ("fwd", ["x", "w", "bias", "scale", "residual", "y"] + _FWD + ["stream"]),
@@ -54,6 +54,9 @@ SPECS = {
 for _stem in ("fi_conv2d_forward", "fi_conv2d_forward_gated", "fi_conv2d_forward_live"):
     for _t in ("bf16", "f16"):
         SPECS["%s_%s" % (_stem, _t)] = SPECS[_stem]
+for _t in ("bf16", "f16"):      # the planned entry of the 16-bit path also takes the weights' 16-bit copy (or NULL)
+    SPECS["fi_conv2d_forward_live_" + _t] = ("fwd", ["x", "w", "w16", "bias", "scale", "residual", "gate", "y"] + _FWD +
+                                             ["live", "stream"])
 for _n in list(SPECS):
     if _n.endswith("_bf16w"):
         SPECS[_n.replace("_bf16w", "_f16w")] = SPECS[_n]
@@ -66,7 +69,8 @@ for _t in ("bf16", "f16"):
 def recorded_entry(name):
     """The launches the replay covers: every fi_conv* / fi_gemm_nt* entry except the host-side queries."""
     return (name.startswith("fi_conv") or name.startswith("fi_gemm_nt")) and \
-        not name.endswith("_eligible") and not name.endswith("_workspace_bytes") and not name.endswith("_plan")
+        not name.endswith("_eligible") and not name.endswith("_workspace_bytes") and \
+        not name.endswith("_plan") and "_plan_" not in name
 
 
 def lowp_dtype(name):
@@ -217,7 +221,9 @@ def _replay_fwd(name, fam, I, nul, ctx):
     worst = 0.0
     for live in (_live_counts(N) if has_live else [None]):
         y = _nan(N, OH, OW, Cout) if ocl else _nan(*out_shape)
-        P = {"x": x, "w": w, "bias": bias, "scale": scale, "residual": residual, "gate": gate, "y": y}
+        # the 16-bit copy where the step handed one over: the same weights in the declared layout
+        w16 = None if nul.get("w16", True) else w.to(dt)
+        P = {"x": x, "w": w, "w16": w16, "bias": bias, "scale": scale, "residual": residual, "gate": gate, "y": y}
         lv = None if live is None else torch.tensor([live], device=DEV, dtype=torch.int32)
         args = []
         for k in SPECS[name][1]:
