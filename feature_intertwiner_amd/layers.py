@@ -459,7 +459,9 @@ def det_target_from_keys(proposals, num_proposals, gt_class_ids, gt_boxes, gt_ma
     ni = torch.gather(neg_idx, 1, (slot - pos_cnt.unsqueeze(1)).clamp(min=0, max=neg_idx.size(1) - 1))
     sel = torch.where(is_pos, pi, ni)
     used = (is_pos | is_neg)
-    rois = torch.gather(proposals, 1, sel.unsqueeze(2).expand(-1, -1, 4)) * used.unsqueeze(2).float()
+    # (where, not a product with the mask: a negative coordinate times 0 left -0.0 in an unused slot; the kernel writes +0)
+    rois = torch.gather(proposals, 1, sel.unsqueeze(2).expand(-1, -1, 4))
+    rois = torch.where(used.unsqueeze(2), rois, torch.zeros_like(rois))
 
     roi_assign = torch.gather(assign, 1, sel)
     roi_gt_boxes = torch.gather(gt_boxes, 1, roi_assign.unsqueeze(2).expand(-1, -1, 4))
