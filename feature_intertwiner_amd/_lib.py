@@ -109,7 +109,10 @@ SIGNATURES = {
     "fi_rows_affine_act": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
     "fi_conv2d_forward_live": (c_int, [c_void_p] * 7 + [c_int] * 16 + [c_void_p, c_void_p]),
     "fi_conv2d_forward_plan": (c_int, [c_void_p] * 7 + [c_int] * 16 + [_ip]),
-    "fi_conv2d_weight_grad_plan": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 12 + [c_void_p, c_int, c_int, _ip]),
+    "fi_conv2d_weight_grad_plan": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 12 + [c_void_p, c_int, c_int, _ip, _ip]),
+    "fi_conv2d_weight_grad_layout": (c_int, [c_void_p, c_void_p] + [c_int] * 11 + [_ip]),
+    "fi_conv2d_weight_grad_plan_bf16": (c_int, [c_void_p] * 4 + [c_int] * 13 + [_ip, _ip]),
+    "fi_conv2d_weight_grad_plan_f16": (c_int, [c_void_p] * 4 + [c_int] * 13 + [_ip, _ip]),
     "fi_gemm_nt_plan": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p, _ip]),
     "fi_weight_transpose_batch": (c_int, [c_void_p, c_int, ctypes.c_long, c_void_p]),
     "fi_conv3x3_forward_bf16w": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p]),
@@ -193,6 +196,26 @@ def conv16_variant(query, *args):
     fi_conv2d_forward_plan_* entry, `args` the launch's arguments up to output_layout."""
     v = ctypes.c_int(-1)
     check(query(*args, ctypes.byref(v)), "fi_conv2d_forward_plan (16-bit)")
+    return v.value
+
+
+# FI_WGRAD16_* of include/fi_capi.h, by value: what fi_conv2d_weight_grad_plan_{bf16,f16} answer with
+WGRAD16_VARIANTS = ("GENERIC", "ROWS", "FLAT")
+WGRAD_BATCH_MAX = 24    # FI_WGRAD_BATCH_MAX
+
+
+def wgrad_plan(query, *args):
+    """(what the launch runs, how many of the n problems it carries): `query` is fi_conv2d_weight_grad_plan (a KERNEL_KEYS
+    id) or fi_conv2d_weight_grad_plan_{bf16,f16} (an index into WGRAD16_VARIANTS), `args` its arguments up to n."""
+    v, per = ctypes.c_int(-1), ctypes.c_int(-1)
+    check(query(*args, ctypes.byref(v), ctypes.byref(per)), "fi_conv2d_weight_grad_plan")
+    return v.value, per.value
+
+
+def wgrad_tap_major(*args):
+    """1 where fi_conv2d_weight_grad accepts weight_layout 1 for x, dy and the geometry in `args`, else 0."""
+    v = ctypes.c_int(-1)
+    check(load().fi_conv2d_weight_grad_layout(*args, ctypes.byref(v)), "fi_conv2d_weight_grad_layout")
     return v.value
 
 _lib = None

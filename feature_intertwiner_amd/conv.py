@@ -548,17 +548,11 @@ def _conv_backward(ctx_needs, x, w, dz, stride, padding, want_db=False, add_to_d
                 dx = dx.expand()
             dx = _relu_mask(dx, gate.contiguous(), dx)
     if ctx_needs[1]:
-        # tap-major dW ([Cout,R,S,Cin]): 128 channels of one tap per column tile, or -- same-size stride-1
-        # layers with Cin == 64 (the C2 stage) -- 64 channels of two taps.  `same` follows wgrad_same_size() and `hwc`
-        # wgrad_checked() in csrc/conv_igemm.hip, which rejects a tap-major request the geometry does not allow
-        same = (stride == (1, 1) and dz.shape[2] == H and dz.shape[3] == W and (H * W) % 4 == 0 and W >= 4 and
-                x.numel() * 4 < 0x7fffff00 and dz.numel() * 4 < 0x7fffff00 and
-                x.data_ptr() % 16 == 0 and dz.data_ptr() % 16 == 0)
-        hwc = 1 if (Cin % 128 == 0 or (Cin == 64 and same)) else 0
+        geom = (N, Cin, H, W, Cout, R, S, stride[0], stride[1], padding[0], padding[1])
         # bf16 weight gradient: always tap-major, so the parameter must be stored that way (or be 1x1)
         bf16 = precision in _LOWP and (R * S == 1 or (Cin % 16 == 0 and w.is_contiguous(memory_format=torch.channels_last)))
-        if bf16:
-            hwc = 1
+        # tap-major dW ([Cout,R,S,Cin]) wherever the fp32 kernels can write it: the library says
+        hwc = 1 if bf16 else _lib.wgrad_tap_major(_lib.ptr(x), _lib.ptr(dz), *geom)
         shape = (Cout, R, S, Cin) if (hwc and R * S > 1) else (Cout, Cin, R, S)
         # pre-zeroed slice of the step's gradient arena (one fill per step instead of one per layer); a repeated
         # use of the layer accumulates into the same slice.  (With want_db the kernel clears dW and db itself.)
@@ -600,30 +594,36 @@ def _conv_backward(ctx_needs, x, w, dz, stride, padding, want_db=False, add_to_d
             # levels): its first use may still be queued together with the pass that scales dW in place -- run the queue
             # before this use adds to the slot, and do not queue this one
             flush_deferred_wgrads()
-        if flags and first and adopt and WGRAD_BATCH > 1 and hwc and same and Cin % 128 == 0 and \
-                (not bf16 or (Cout % 64 == 0 and (R * S == 1 or (R, S, padding) == (3, 3, (1, 1))))) and \
-                N * dz.shape[2] * dz.shape[3] <= WGRAD_BATCH_MAX_PIXELS and _defer_wgrad(
-                    (N, Cin, H, W, Cout, R, S, padding, want_db and db is not None, precision if bf16 else None),
-                    x, dz, dw, db if want_db else None, after_wgrad, bool(hwc and R * S > 1), dz_ready,
-                    torch.cuda.current_stream(x.device), side):
-            side = None                    # queued: launched with the other layers of its geometry (_flush_wgrads)
-            deferred = True
-        else:
-            deferred = False
+        # queued for a launch together with the other layers of its geometry (_flush_wgrads): where the library would put
+        # several such problems into one launch
+        deferred = False
+        if flags and first and adopt and WGRAD_BATCH > 1 and N * dz.shape[2] * dz.shape[3] <= WGRAD_BATCH_MAX_PIXELS and \
+                Cin % 128 == 0:         # policy: batching was only measured on the C3-C5 blocks (profiles/r04_ab_wgrad_*.txt)
+            nq = min(WGRAD_BATCH, _lib.WGRAD_BATCH_MAX)
+            if bf16:
+                per = _lib.wgrad_plan(_lowp_fn(L, "conv2d_weight_grad_plan", precision), _lib.ptr(x), _lib.ptr(dz),
+                                      _lib.ptr(dw), _lib.ptr(db), *geom, flags, nq)[1]
+            else:
+                per = _lib.wgrad_plan(L.fi_conv2d_weight_grad_plan, _lib.ptr(x), _lib.ptr(dz), _lib.ptr(dw), *geom, hwc,
+                                      _lib.ptr(db), flags, nq)[1]
+            deferred = per > 1 and _defer_wgrad(
+                (N, Cin, H, W, Cout, R, S, padding, want_db and db is not None, precision if bf16 else None),
+                x, dz, dw, db if want_db else None, after_wgrad, bool(hwc and R * S > 1), dz_ready,
+                torch.cuda.current_stream(x.device), side)
+            if deferred:
+                side = None
         with torch.cuda.device(x.device), (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
             if deferred:
                 pass
             elif bf16:
                 _log_flops("conv_bf16_wgrad", 2 * N * Cout * dz.shape[2] * dz.shape[3] * Cin * R * S)
                 _lib.check(_lowp_fn(L, "conv2d_weight_grad_db", precision)(_lib.ptr(x), _lib.ptr(dz), _lib.ptr(dw), _lib.ptr(db),
-                                                        N, Cin, H, W, Cout,
-                                                        R, S, stride[0], stride[1], padding[0], padding[1], flags,
-                                                        _lib.current_stream()), "fi_conv2d_weight_grad_bf16")
+                                                                           *geom, flags, _lib.current_stream()),
+                           "fi_conv2d_weight_grad_bf16")
             else:
-                args = (_lib.ptr(x), _lib.ptr(dz), _lib.ptr(dw), N, Cin, H, W, Cout, R, S, stride[0], stride[1], padding[0],
-                        padding[1], hwc, _lib.ptr(db), flags, _lib.current_stream())
+                args = (_lib.ptr(x), _lib.ptr(dz), _lib.ptr(dw), *geom, hwc, _lib.ptr(db), flags, _lib.current_stream())
                 if FLOP_LOG is not None:
-                    _log_flops(_lib.planned_kernel(L.fi_conv2d_weight_grad_plan, *args[:-1], 1),
+                    _log_flops(_lib.KERNEL_KEYS[_lib.wgrad_plan(L.fi_conv2d_weight_grad_plan, *args[:-1], 1)[0]],
                                2 * N * Cout * dz.shape[2] * dz.shape[3] * Cin * R * S)
                 _lib.check(L.fi_conv2d_weight_grad(*args), "fi_conv2d_weight_grad")
             if after_wgrad is not None and not deferred:
@@ -715,7 +715,7 @@ def _defer_wgrad(key, x, dz, dw, db, after, tap_major, ev, main, side):
     # reference to that very object makes it clone the still-empty slot)
     e["items"].append((x, dz, dw.view(dw.shape), None if db is None else db.view(db.shape), after, tap_major, ev))
     e["last"] = q["tick"]
-    if len(e["items"]) >= min(WGRAD_BATCH, 24):
+    if len(e["items"]) >= min(WGRAD_BATCH, _lib.WGRAD_BATCH_MAX):
         _flush_wgrads(key)
     return True
 
@@ -748,8 +748,9 @@ def _flush_wgrads(key):
         if lowp:
             _log_flops("conv_bf16_wgrad", 2.0 * n * N * H * W * Cout * Cin * R * S)
         elif FLOP_LOG is not None:         # (the batch entry takes pointer tables: the query gets the first problem and n)
-            _log_flops(_lib.planned_kernel(L.fi_conv2d_weight_grad_plan, _lib.ptr(xs[0]), _lib.ptr(dzs[0]), _lib.ptr(dws[0]),
-                                           *geom, _lib.ptr(items[0][3]) if has_db else None, _lib.OUTPUTS_ZEROED, n),
+            _log_flops(_lib.KERNEL_KEYS[_lib.wgrad_plan(L.fi_conv2d_weight_grad_plan, _lib.ptr(xs[0]), _lib.ptr(dzs[0]),
+                                                        _lib.ptr(dws[0]), *geom, _lib.ptr(items[0][3]) if has_db else None,
+                                                        _lib.OUTPUTS_ZEROED, n)[0]],
                        2.0 * n * N * H * W * Cout * Cin * R * S)
         fn = _lowp_fn(L, "conv2d_weight_grad_batch", lowp) if lowp else L.fi_conv2d_weight_grad_batch
         _lib.check(fn(arr(xs), arr(dzs), arr(dws), arr([it[3] for it in items]) if has_db else None, n, *geom,

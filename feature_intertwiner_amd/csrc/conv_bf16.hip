@@ -1798,6 +1798,186 @@ int launch_reg1x1(const float *x, const uint16_t *w16, const Epi &ep, float *y, 
     return FI_OK;
 }
 
+// -------------------------------------------------------------------------------------
+// Kernel selection of the weight gradient, as plan_forward16 does it for the forward path.  plan_wgrad16 validates the
+// arguments of fi_conv2d_weight_grad_db_<p> and decides which of the three kernels the call runs, on which tiles and
+// splits, and how many problems of one geometry the launch carries -- host arithmetic on sizes and pointer VALUES, no HIP
+// call.  wgrad16_impl (behind every weight-gradient entry of this file) launches exactly what the plan says,
+// fi_conv2d_weight_grad_batch_<p> cuts its problems into launches of plan.per_launch, and
+// fi_conv2d_weight_grad_plan_<p> answers callers that need the plan without a launch (conv._conv_backward: is this layer
+// worth queueing for a batched launch).
+// -------------------------------------------------------------------------------------
+// conv_bf16_wgrad_flat_kernel: 3x3 / pad 1 or 1x1 / pad 0 at stride 1, whole quads of pixels and at least one K-tile per
+// image, whole 64-channel tiles on both sides, byte offsets that fit its buffer descriptors, 16-byte loads
+bool wgrad_flat_shape(const Geom &g, const float *x, const float *dy)
+{
+    const bool k3 = g.R == 3 && g.S == 3 && g.ph == 1 && g.pw == 1, k1 = g.R == 1 && g.S == 1 && g.ph == 0 && g.pw == 0;
+    if (!(k3 || k1) || g.sh != 1 || g.sw != 1 || g.OH != g.H || g.OW != g.W) return false;
+    const int HW = g.OH * g.OW;
+    return HW % 4 == 0 && HW >= FK && g.W >= 4 && g.Cout % 64 == 0 && g.Cin % 64 == 0 &&
+           (size_t)g.N * g.Cin * HW * 4 < 0x7fffff00ULL && (size_t)g.N * g.Cout * HW * 4 < 0x7fffff00ULL &&
+           (uintptr_t)x % 16 == 0 && (uintptr_t)dy % 16 == 0 && !getenv("FI_NO_BF16_FLAT");
+}
+
+struct WgradPlan16 {
+    int variant;                           // FI_WGRAD16_*
+    int bm, bnc, mt, cin_tiles;            // tile of output x input channels, and the tile counts
+    int z;                                 // splits of the reduction over pixels
+    int ktiles, per;                       // FLAT, ROWS: K-tiles in all and per split
+    int chunks_per_image, chunk_pixels;    // GENERIC: the pixel chunks the splits walk
+    dim3 grid;
+    int per_launch;                        // problems of this geometry the launch carries (1: the batch entry loops)
+};
+
+// fi_conv2d_weight_grad_db_<p>'s arguments (without dbias and the stream) -> g (all but n_live) and the plan of the first
+// launch for n problems of this geometry, x / dy / dweight being those of the first.  batch: the caller can hand the
+// problems over in a WgradBatch16 (uniform bias use, every x and dy 16-byte aligned).
+int plan_wgrad16(Geom &g, WgradPlan16 &p, const float *x, const float *dy, const float *dweight, int N, int Cin, int H,
+                 int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int flags, int n,
+                 bool batch)
+{
+    const int rc = make_geom(g, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w, 0, 0);
+    if (rc != FI_OK) return rc;
+    FI_REQUIRE(x && dy && dweight, "null pointer");
+    FI_REQUIRE(n >= 1, "empty batch / null pointer table");
+    p = WgradPlan16{};
+    p.per_launch = 1;
+    const int RS = R * S;
+    if (wgrad_flat_shape(g, x, dy)) {
+        // same-size stride-1 layers with whole channel tiles: flat pixel space
+        p.variant = FI_WGRAD16_FLAT;
+        if (batch && n > 1 && (flags & FI_OUTPUTS_ZEROED)) p.per_launch = std::min(n, FI_WGRAD_BATCH_MAX);
+        p.bm = Cout % 128 == 0 ? 128 : 64;
+        p.bnc = Cin % 128 == 0 ? 128 : 64;
+        p.mt = Cout / p.bm;
+        p.cin_tiles = Cin / p.bnc;
+        const long tiles = (long)p.mt * RS * p.cin_tiles;
+        p.ktiles = fi::ceil_div(g.P, FK);
+        // split the pixel range so that ~2048 workgroups exist, at least 8 K-tiles each; a batch fills the chip
+        // together: fewer, longer splits each
+        static const int target_wg = getenv("FI_WG16_TARGET") ? atoi(getenv("FI_WG16_TARGET")) : 2048;    // (tuning knob)
+        long z = target_wg / (tiles * p.per_launch);
+        if (z < 1) z = 1;
+        if (z > p.ktiles / 8) z = p.ktiles / 8 > 0 ? p.ktiles / 8 : 1;
+        if (N == 1 && H == 1 && !batch) {
+            // the kernel as a GEMM (conv.linear: one long reduction): every split ends with a 64 KB atomic epilogue, so
+            // a split should cover >= 3072 elements of the reduction as long as the chip still gets a workgroup per CU
+            // (scripts/gemm16_probe.py: 2048 x 1024 x 12544 163 -> 111 us, 1408 x 1024 x 25088 180 -> 150 us)
+            long zmax = g.P / 3072, zmin = fi::ceil_div(256, (int)tiles);
+            if (zmax < zmin) zmax = zmin;
+            if (z > zmax) z = zmax;
+        }
+        if (z > 65535) z = 65535;
+        p.per = fi::ceil_div(p.ktiles, (int)z);
+        p.z = fi::ceil_div(p.ktiles, p.per);
+        FI_REQUIRE((long)RS * p.cin_tiles <= 65535, "too many (tap, ci) tiles");
+        const long nblk = tiles * p.z * p.per_launch;
+        FI_REQUIRE(nblk + 8 < 2147483647L, "too many workgroups");
+        p.grid = dim3((unsigned)(((nblk + 7) / 8) * 8));
+        return FI_OK;
+    }
+    if ((stride_w == 1 || stride_w == 2) && g.OW >= 4 && W >= 4 * stride_w) {
+        // rows of pixel quads (conv_bf16_wgrad_kernel)
+        p.variant = FI_WGRAD16_ROWS;
+        p.bm = Cout <= 64 ? 64 : 128;
+        p.bnc = Cin <= 64 ? 64 : 128;
+        p.mt = fi::ceil_div(Cout, p.bm);
+        p.cin_tiles = fi::ceil_div(Cin, p.bnc);
+        const long tiles = (long)p.mt * RS * p.cin_tiles;
+        const long tq = (long)N * g.OH * ((g.OW + 3) / 4);
+        FI_REQUIRE(tq * 4 < 2147483647L, "too many pixels");
+        p.ktiles = (int)((tq + 7) / 8);
+        // split the reduction so that ~2048 workgroups exist, at least 8 K-tiles each
+        long z = 2048 / tiles;
+        if (z < 1) z = 1;
+        if (z > p.ktiles / 8) z = p.ktiles / 8 > 0 ? p.ktiles / 8 : 1;
+        if (z > 65535) z = 65535;
+        p.per = fi::ceil_div(p.ktiles, (int)z);
+        p.z = fi::ceil_div(p.ktiles, p.per);
+    } else {
+        // generic form (strided layers, maps narrower than 4): split the reduction (N images x chunks of pixels)
+        // so that ~2048 workgroups exist; a chunk is a multiple of 32 pixels and never crosses an image
+        p.variant = FI_WGRAD16_GENERIC;
+        p.bm = 128;
+        p.bnc = TN;
+        p.mt = fi::ceil_div(Cout, p.bm);
+        p.cin_tiles = fi::ceil_div(Cin, p.bnc);
+        const long tiles = (long)p.mt * RS * p.cin_tiles;
+        const int OHW = g.OH * g.OW;
+        long want = 2048 / tiles;
+        if (want < 1) want = 1;
+        p.chunks_per_image = 1;
+        if (want > N) p.chunks_per_image = (int)((want + N - 1) / N);
+        p.chunk_pixels = fi::ceil_div(fi::ceil_div(OHW, p.chunks_per_image), TK) * TK;
+        if (p.chunk_pixels < 4 * TK) p.chunk_pixels = 4 * TK;
+        p.chunks_per_image = fi::ceil_div(OHW, p.chunk_pixels);
+        long z = (long)N * p.chunks_per_image;
+        if (z > want) z = want;
+        if (z > 65535) z = 65535;
+        p.z = (int)z;
+    }
+    FI_REQUIRE((long)RS * p.cin_tiles <= 65535, "too many (tap, ci) tiles");
+    p.grid = dim3(p.mt, RS * p.cin_tiles, (unsigned)p.z);
+    return FI_OK;
+}
+
+// Every weight-gradient entry of this file: plan, clear the outputs unless the caller did, launch what the plan says.
+// batch: the problems of a fi_conv2d_weight_grad_batch_<p> launch (x, dy, dweight, dbias: those of its first);
+// rows_live_dev: see fi_conv2d_weight_grad_rows_<p> (only the flat kernel reads it).
+int wgrad16_impl(const float *x, const float *dy, float *dweight, float *dbias, int N, int Cin, int H, int W, int Cout,
+                 int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int flags, fi_stream_t stream,
+                 const WgradBatch16 *batch, const int32_t *rows_live_dev = nullptr)
+{
+    Geom g;
+    WgradPlan16 p;
+    const int rc = plan_wgrad16(g, p, x, dy, dweight, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w, flags,
+                                batch ? batch->n : 1, batch != nullptr);
+    if (rc != FI_OK) return rc;
+    FI_REQUIRE(!batch || (p.variant == FI_WGRAD16_FLAT && p.per_launch == batch->n),
+               "internal: a batch of weight gradients handed to a plan that does not carry it");
+    g.n_live = rows_live_dev;
+    hipStream_t st = (hipStream_t)stream;
+    if (!(flags & FI_OUTPUTS_ZEROED)) {
+        FI_HIP_CHECK(hipMemsetAsync(dweight, 0, sizeof(float) * (size_t)Cout * R * S * Cin, st));
+        if (dbias) FI_HIP_CHECK(hipMemsetAsync(dbias, 0, sizeof(float) * (size_t)Cout, st));
+    }
+    fi::ProfScope prof(FI_K_CONV_BF16_WGRAD, st);
+    if (dbias && p.variant != FI_WGRAD16_FLAT) {           // (the flat kernel sums the dY tiles it stages)
+        const int chunks = std::max(1, std::min(N, 2048 / std::max(1, Cout)));
+        hipLaunchKernelGGL(channel_sum_kernel, dim3((unsigned)Cout, (unsigned)chunks), dim3(256), 0, st, dy, dbias, N, Cout,
+                           g.OH * g.OW);
+        FI_HIP_CHECK(hipGetLastError());
+    }
+    const bool b128 = p.bm == 128, c128 = p.bnc == 128;
+    switch (p.variant) {
+    case FI_WGRAD16_FLAT: {
+        auto k = R == 3 ? (b128 ? (c128 ? conv_bf16_wgrad_flat_kernel<128, 128, true> : conv_bf16_wgrad_flat_kernel<128, 64, true>)
+                                : (c128 ? conv_bf16_wgrad_flat_kernel<64, 128, true> : conv_bf16_wgrad_flat_kernel<64, 64, true>))
+                        : (b128 ? (c128 ? conv_bf16_wgrad_flat_kernel<128, 128, false> : conv_bf16_wgrad_flat_kernel<128, 64, false>)
+                                : (c128 ? conv_bf16_wgrad_flat_kernel<64, 128, false> : conv_bf16_wgrad_flat_kernel<64, 64, false>));
+        WgradBatch16 wb;
+        wb.n = 0;
+        if (batch) wb = *batch;
+        hipLaunchKernelGGL(k, p.grid, dim3(kThreads), 0, st, x, dy, dweight, g, p.cin_tiles, p.per * FK, p.mt, p.z, dbias, wb);
+        break;
+    }
+    case FI_WGRAD16_ROWS: {
+        const bool s2 = stride_w == 2;
+        auto k = b128 ? (c128 ? (s2 ? conv_bf16_wgrad_kernel<128, 128, 2> : conv_bf16_wgrad_kernel<128, 128, 1>)
+                              : (s2 ? conv_bf16_wgrad_kernel<128, 64, 2> : conv_bf16_wgrad_kernel<128, 64, 1>))
+                      : (c128 ? (s2 ? conv_bf16_wgrad_kernel<64, 128, 2> : conv_bf16_wgrad_kernel<64, 128, 1>)
+                              : (s2 ? conv_bf16_wgrad_kernel<64, 64, 2> : conv_bf16_wgrad_kernel<64, 64, 1>));
+        hipLaunchKernelGGL(k, p.grid, dim3(kThreads), 0, st, x, dy, dweight, g, p.cin_tiles, p.ktiles, p.per);
+        break;
+    }
+    default:
+        hipLaunchKernelGGL(conv_bf16_wgrad_generic_kernel, p.grid, dim3(kThreads), 0, st, x, dy, dweight, g, p.cin_tiles,
+                           p.chunks_per_image, p.chunk_pixels);
+    }
+    FI_HIP_CHECK(hipGetLastError());
+    return FI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1930,10 +2110,6 @@ int FI16(fi_conv2d_weight_grad, )(const float *x, const float *dy, float *dweigh
                                             pad_w, flags, stream);
 }
 
-static int wgrad16_impl(const float *x, const float *dy, float *dweight, float *dbias, int N, int Cin, int H,
-                        int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
-                        int flags, fi_stream_t stream, const WgradBatch16 *batch, const int32_t *rows_live_dev = nullptr);
-
 int FI16(fi_conv2d_weight_grad_db, )(const float *x, const float *dy, float *dweight, float *dbias, int N, int Cin, int H,
                                   int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
                                   int flags, fi_stream_t stream)
@@ -1952,8 +2128,7 @@ int FI16(fi_conv2d_weight_grad_rows, )(const float *x, const float *dy, float *d
                         nullptr, rows_live_dev);
 }
 
-// n weight gradients of one geometry in one launch (see fi_conv2d_weight_grad_batch); loops when the geometry is not
-// the flat kernel's or the outputs are not pre-zeroed
+// n weight gradients of one geometry (see fi_conv2d_weight_grad_batch): in launches of as many problems as the plan says
 int FI16(fi_conv2d_weight_grad_batch, )(const float *const *x, const float *const *dy, float *const *dweight,
                                      float *const *dbias, int n, int N, int Cin, int H, int W, int Cout, int R, int S,
                                      int stride_h, int stride_w, int pad_h, int pad_w, int weight_layout, int flags,
@@ -1961,149 +2136,54 @@ int FI16(fi_conv2d_weight_grad_batch, )(const float *const *x, const float *cons
 {
     (void)weight_layout;                                  // the 16-bit kernels always write tap-major
     FI_REQUIRE(n >= 1 && x && dy && dweight, "empty batch / null pointer table");
-    const bool k3 = R == 3 && S == 3 && pad_h == 1 && pad_w == 1, k1 = R == 1 && S == 1 && pad_h == 0 && pad_w == 0;
-    const int HWf = H * W;
-    bool ok = (k3 || k1) && stride_h == 1 && stride_w == 1 && HWf % 4 == 0 && HWf >= FK && W >= 4 && Cout % 64 == 0 &&
-              Cin % 64 == 0 && (flags & FI_OUTPUTS_ZEROED) && n > 1 && !getenv("FI_NO_BF16_FLAT");
-    bool any_db = false, all_db = true;
+    bool aligned = true, any_db = false, all_db = true;
     for (int i = 0; i < n; ++i) {
         FI_REQUIRE(x[i] && dy[i] && dweight[i], "null pointer in the batch");
-        ok = ok && (uintptr_t)x[i] % 16 == 0 && (uintptr_t)dy[i] % 16 == 0;
+        aligned = aligned && (uintptr_t)x[i] % 16 == 0 && (uintptr_t)dy[i] % 16 == 0;
         const bool has = dbias && dbias[i];
         any_db = any_db || has;
         all_db = all_db && has;
     }
-    if (!ok || (any_db && !all_db)) {
+    Geom g;
+    WgradPlan16 p;
+    int rc = plan_wgrad16(g, p, x[0], dy[0], dweight[0], N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w, flags,
+                          n, aligned && (all_db || !any_db));
+    if (rc != FI_OK) return rc;
+    if (p.per_launch == 1) {
         for (int i = 0; i < n; ++i) {
-            const int rc = wgrad16_impl(x[i], dy[i], dweight[i], dbias ? dbias[i] : nullptr, N, Cin, H, W, Cout, R, S,
-                                        stride_h, stride_w, pad_h, pad_w, flags, stream, nullptr);
+            rc = wgrad16_impl(x[i], dy[i], dweight[i], dbias ? dbias[i] : nullptr, N, Cin, H, W, Cout, R, S, stride_h,
+                              stride_w, pad_h, pad_w, flags, stream, nullptr);
             if (rc != FI_OK) return rc;
         }
         return FI_OK;
     }
-    for (int i0 = 0; i0 < n; i0 += FI_WGRAD_BATCH_MAX) {
+    for (int i0 = 0; i0 < n; i0 += p.per_launch) {
         WgradBatch16 wb;
-        wb.n = n - i0 < FI_WGRAD_BATCH_MAX ? n - i0 : FI_WGRAD_BATCH_MAX;
+        wb.n = std::min(n - i0, p.per_launch);
         for (int i = 0; i < FI_WGRAD_BATCH_MAX; ++i) {
             const int j = i0 + (i < wb.n ? i : 0);
             wb.x[i] = x[j]; wb.dy[i] = dy[j]; wb.dw[i] = dweight[j]; wb.db[i] = all_db ? dbias[j] : nullptr;
         }
-        const int rc = wgrad16_impl(wb.x[0], wb.dy[0], wb.dw[0], wb.db[0], N, Cin, H, W, Cout, R, S, stride_h, stride_w,
-                                    pad_h, pad_w, flags, stream, &wb);
+        rc = wgrad16_impl(wb.x[0], wb.dy[0], wb.dw[0], wb.db[0], N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w,
+                          flags, stream, &wb);
         if (rc != FI_OK) return rc;
     }
     return FI_OK;
 }
 
-static int wgrad16_impl(const float *x, const float *dy, float *dweight, float *dbias, int N, int Cin, int H,
-                        int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
-                        int flags, fi_stream_t stream, const WgradBatch16 *batch, const int32_t *rows_live_dev)
+int FI16(fi_conv2d_weight_grad_plan, )(const float *x, const float *dy, float *dweight, float *dbias, int N, int Cin,
+                                    int H, int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
+                                    int flags, int n, int *variant, int *per_launch)
 {
+    (void)dbias;                                          // given for all problems or for none
+    FI_REQUIRE(variant != nullptr, "null pointer");
     Geom g;
-    int rc = make_geom(g, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w, 0, 0);
+    WgradPlan16 p;
+    const int rc = plan_wgrad16(g, p, x, dy, dweight, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w, flags, n,
+                                n > 1);
     if (rc != FI_OK) return rc;
-    FI_REQUIRE(x && dy && dweight, "null pointer");
-    g.n_live = rows_live_dev;            // only the flat kernel reads it
-    hipStream_t st = (hipStream_t)stream;
-    const int RS = R * S;
-    if (!(flags & FI_OUTPUTS_ZEROED)) {
-        FI_HIP_CHECK(hipMemsetAsync(dweight, 0, sizeof(float) * (size_t)Cout * RS * Cin, st));
-        if (dbias) FI_HIP_CHECK(hipMemsetAsync(dbias, 0, sizeof(float) * (size_t)Cout, st));
-    }
-    const int OHW = g.OH * g.OW;
-    fi::ProfScope prof(FI_K_CONV_BF16_WGRAD, st);
-    // same-size stride-1 layers with whole channel tiles: flat pixel space (conv_bf16_wgrad_flat_kernel)
-    {
-        const bool k3 = R == 3 && S == 3 && pad_h == 1 && pad_w == 1, k1 = R == 1 && S == 1 && pad_h == 0 && pad_w == 0;
-        const int HWf = H * W;
-        const int bm = Cout % 128 == 0 ? 128 : (Cout % 64 == 0 ? 64 : 0), bnc = Cin % 128 == 0 ? 128 : (Cin % 64 == 0 ? 64 : 0);
-        if ((k3 || k1) && stride_h == 1 && stride_w == 1 && g.OH == H && g.OW == W && HWf % 4 == 0 && HWf >= FK && W >= 4 &&
-            bm && bnc && (size_t)N * Cin * HWf * 4 < 0x7fffff00ULL && (size_t)N * Cout * HWf * 4 < 0x7fffff00ULL &&
-            (uintptr_t)x % 16 == 0 && (uintptr_t)dy % 16 == 0 && !getenv("FI_NO_BF16_FLAT")) {
-            const int mt = Cout / bm, cin_tiles = Cin / bnc;
-            const long tiles = (long)mt * RS * cin_tiles;
-            const int ptiles = fi::ceil_div(g.P, FK);
-            // split the pixel range so that ~2048 workgroups exist, at least 8 K-tiles each
-            const int nb = batch ? batch->n : 1;            // a batch fills the chip together: fewer, longer splits each
-            static const int target_wg = getenv("FI_WG16_TARGET") ? atoi(getenv("FI_WG16_TARGET")) : 2048;    // (tuning knob)
-            long z = target_wg / (tiles * nb);
-            if (z < 1) z = 1;
-            if (z > ptiles / 8) z = ptiles / 8 > 0 ? ptiles / 8 : 1;
-            if (N == 1 && H == 1 && !batch) {
-                // the kernel as a GEMM (conv.linear: one long reduction): every split ends with a 64 KB atomic epilogue, so
-                // a split should cover >= 3072 elements of the reduction as long as the chip still gets a workgroup per CU
-                // (scripts/gemm16_probe.py: 2048 x 1024 x 12544 163 -> 111 us, 1408 x 1024 x 25088 180 -> 150 us)
-                long zmax = g.P / 3072, zmin = fi::ceil_div(256, (int)tiles);
-                if (zmax < zmin) zmax = zmin;
-                if (z > zmax) z = zmax;
-            }
-            if (z > 65535) z = 65535;
-            const int per = fi::ceil_div(ptiles, (int)z);
-            z = fi::ceil_div(ptiles, per);
-            FI_REQUIRE((long)RS * cin_tiles <= 65535, "too many (tap, ci) tiles");
-            const long nblk = tiles * z * nb;
-            FI_REQUIRE(nblk + 8 < 2147483647L, "too many workgroups");
-            const dim3 grid((unsigned)(((nblk + 7) / 8) * 8));
-            auto k = k3 ? (bm == 128 ? (bnc == 128 ? conv_bf16_wgrad_flat_kernel<128, 128, true> : conv_bf16_wgrad_flat_kernel<128, 64, true>)
-                                     : (bnc == 128 ? conv_bf16_wgrad_flat_kernel<64, 128, true> : conv_bf16_wgrad_flat_kernel<64, 64, true>))
-                        : (bm == 128 ? (bnc == 128 ? conv_bf16_wgrad_flat_kernel<128, 128, false> : conv_bf16_wgrad_flat_kernel<128, 64, false>)
-                                     : (bnc == 128 ? conv_bf16_wgrad_flat_kernel<64, 128, false> : conv_bf16_wgrad_flat_kernel<64, 64, false>));
-            WgradBatch16 wb;
-            wb.n = 0;
-            if (batch) wb = *batch;
-            hipLaunchKernelGGL(k, grid, dim3(kThreads), 0, st, x, dy, dweight, g, cin_tiles, per * FK, mt, (int)z, dbias, wb);
-            FI_HIP_CHECK(hipGetLastError());
-            return FI_OK;
-        }
-    }
-    if (dbias) {
-        const int chunks = std::max(1, std::min(N, 2048 / std::max(1, Cout)));
-        hipLaunchKernelGGL(channel_sum_kernel, dim3((unsigned)Cout, (unsigned)chunks), dim3(256), 0, st, dy, dbias, N, Cout, OHW);
-        FI_HIP_CHECK(hipGetLastError());
-    }
-    if ((stride_w == 1 || stride_w == 2) && g.OW >= 4 && W >= 4 * stride_w) {
-        const int bm = Cout <= 64 ? 64 : 128, bnc = Cin <= 64 ? 64 : 128;
-        const int mt = fi::ceil_div(Cout, bm), cin_tiles = fi::ceil_div(Cin, bnc);
-        const long tiles = (long)mt * RS * cin_tiles;
-        const long tq = (long)N * g.OH * ((g.OW + 3) / 4);
-        FI_REQUIRE(tq * 4 < 2147483647L, "too many pixels");
-        const int ktiles_total = (int)((tq + 7) / 8);
-        // split the reduction so that ~2048 workgroups exist, at least 8 K-tiles each
-        long z = 2048 / tiles;
-        if (z < 1) z = 1;
-        if (z > ktiles_total / 8) z = ktiles_total / 8 > 0 ? ktiles_total / 8 : 1;
-        if (z > 65535) z = 65535;
-        const int per = fi::ceil_div(ktiles_total, (int)z);
-        z = fi::ceil_div(ktiles_total, per);
-        FI_REQUIRE((long)RS * cin_tiles <= 65535, "too many (tap, ci) tiles");
-        const dim3 grid(mt, RS * cin_tiles, (unsigned)z);
-        const bool s2 = stride_w == 2;
-        auto k = bm == 128 ? (bnc == 128 ? (s2 ? conv_bf16_wgrad_kernel<128, 128, 2> : conv_bf16_wgrad_kernel<128, 128, 1>)
-                                         : (s2 ? conv_bf16_wgrad_kernel<128, 64, 2> : conv_bf16_wgrad_kernel<128, 64, 1>))
-                           : (bnc == 128 ? (s2 ? conv_bf16_wgrad_kernel<64, 128, 2> : conv_bf16_wgrad_kernel<64, 128, 1>)
-                                         : (s2 ? conv_bf16_wgrad_kernel<64, 64, 2> : conv_bf16_wgrad_kernel<64, 64, 1>));
-        hipLaunchKernelGGL(k, grid, dim3(kThreads), 0, st, x, dy, dweight, g, cin_tiles, ktiles_total, per);
-        FI_HIP_CHECK(hipGetLastError());
-        return FI_OK;
-    }
-    const int mt = fi::ceil_div(Cout, 128), cin_tiles = fi::ceil_div(Cin, TN);
-    const long tiles = (long)mt * RS * cin_tiles;
-    // generic form (strided layers, maps narrower than 4): split the reduction (N images x chunks of pixels)
-    // so that ~2048 workgroups exist; a chunk is a multiple of 32 pixels and never crosses an image
-    long want = 2048 / tiles;
-    if (want < 1) want = 1;
-    int chunks_per_image = 1;
-    if (want > N) chunks_per_image = (int)((want + N - 1) / N);
-    int chunk_pixels = fi::ceil_div(fi::ceil_div(OHW, chunks_per_image), TK) * TK;
-    if (chunk_pixels < 4 * TK) chunk_pixels = 4 * TK;
-    chunks_per_image = fi::ceil_div(OHW, chunk_pixels);
-    long z = (long)N * chunks_per_image;
-    if (z > want) z = want;
-    if (z > 65535) z = 65535;
-    FI_REQUIRE((long)RS * cin_tiles <= 65535, "too many (tap, ci) tiles");
-    hipLaunchKernelGGL(conv_bf16_wgrad_generic_kernel, dim3(mt, RS * cin_tiles, (unsigned)z), dim3(kThreads), 0, st, x, dy,
-                       dweight, g, cin_tiles, chunks_per_image, chunk_pixels);
-    FI_HIP_CHECK(hipGetLastError());
+    *variant = p.variant;
+    if (per_launch) *per_launch = p.per_launch;
     return FI_OK;
 }
 

@@ -2563,6 +2563,13 @@ static bool wgrad_batchable(const ConvGeom &g, const float *x, const float *dy, 
     return hwc && wgrad_same_size(g, x, dy);
 }
 
+// tap-major dW: 128 input channels of one tap per column tile, or (Cin == 64, row-major kernel only) the 64 channels
+// of two taps
+static bool wgrad_tap_major_ok(const ConvGeom &g, const float *x, const float *dy)
+{
+    return g.Cin % BN == 0 || (g.Cin == 64 && wgrad_same_size(g, x, dy));
+}
+
 // fi_conv2d_weight_grad's argument checks -> g (all but zero) and hwc
 static int wgrad_checked(ConvGeom &g, bool &hwc, const float *x, const float *dy, const float *dweight, int N, int Cin, int H,
                          int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int weight_layout)
@@ -2571,10 +2578,7 @@ static int wgrad_checked(ConvGeom &g, bool &hwc, const float *x, const float *dy
     if (rc != FI_OK) return rc;
     FI_REQUIRE(x && dy && dweight, "null pointer");
     FI_REQUIRE(weight_layout == 0 || weight_layout == 1, "weight_layout: 0 = [Cout][Cin][R][S], 1 = [Cout][R][S][Cin]");
-    // tap-major dW: 128 input channels of one tap per column tile, or (Cin == 64, row-major kernel only)
-    // the 64 channels of two taps
-    const bool half = (Cin == 64) && wgrad_same_size(g, x, dy);
-    hwc = ((Cin % BN == 0) || half) && (weight_layout == 1 || R * S == 1);
+    hwc = wgrad_tap_major_ok(g, x, dy) && (weight_layout == 1 || R * S == 1);
     FI_REQUIRE(hwc || weight_layout == 0,
                "weight_layout 1 needs Cin % 128 == 0, or Cin == 64 on a same-size stride-1 layer");
     return FI_OK;
@@ -2676,7 +2680,7 @@ static int wgrad_impl(const float *x, const float *dy, float *dweight, int N, in
 
 int fi_conv2d_weight_grad_plan(const float *x, const float *dy, float *dweight, int N, int Cin, int H, int W, int Cout,
                                int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int weight_layout,
-                               float *dbias, int flags, int n, int *kernel_id)
+                               float *dbias, int flags, int n, int *kernel_id, int *per_launch)
 {
     FI_REQUIRE(kernel_id != nullptr, "null pointer");
     FI_REQUIRE(n >= 1, "empty batch / null pointer table");
@@ -2685,7 +2689,20 @@ int fi_conv2d_weight_grad_plan(const float *x, const float *dy, float *dweight, 
     const int rc = wgrad_checked(g, hwc, x, dy, dweight, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w,
                                  weight_layout);
     if (rc != FI_OK) return rc;
-    *kernel_id = wgrad_conv_plan(g, wgrad_batch_size(wgrad_batchable(g, x, dy, weight_layout), n, flags, true)).kernel_id;
+    const int nb = wgrad_batch_size(wgrad_batchable(g, x, dy, weight_layout), n, flags, true);
+    *kernel_id = wgrad_conv_plan(g, nb).kernel_id;
+    if (per_launch) *per_launch = nb;
+    return FI_OK;
+}
+
+int fi_conv2d_weight_grad_layout(const float *x, const float *dy, int N, int Cin, int H, int W, int Cout, int R, int S,
+                                 int stride_h, int stride_w, int pad_h, int pad_w, int *weight_layout)
+{
+    FI_REQUIRE(weight_layout != nullptr, "null pointer");
+    ConvGeom g;
+    const int rc = make_geom(g, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w);
+    if (rc != FI_OK) return rc;
+    *weight_layout = wgrad_tap_major_ok(g, x, dy) ? 1 : 0;
     return FI_OK;
 }
 

@@ -414,18 +414,24 @@ int fi_conv2d_weight_grad(const float *x, const float *dy, float *dweight, int N
                           int pad_h, int pad_w, int weight_layout, float *dbias, int flags,
                           fi_stream_t stream);
 /* The same query for fi_conv2d_weight_grad (n = 1) and for the first launch of fi_conv2d_weight_grad_batch with n problems
- * of this geometry, x / dy / dweight being those of its first problem and dbias given for all problems or for none. */
+ * of this geometry, x / dy / dweight being those of its first problem and dbias given for all problems or for none.
+ * per_launch (may be NULL): how many of the n problems that launch carries; 1 means the batch entry loops. */
 int fi_conv2d_weight_grad_plan(const float *x, const float *dy, float *dweight, int N, int Cin, int H, int W, int Cout,
                                int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int weight_layout,
-                               float *dbias, int flags, int n, int *kernel_id);
+                               float *dbias, int flags, int n, int *kernel_id, int *per_launch);
+/* Which dW layout fi_conv2d_weight_grad accepts for this geometry and these pointers (host-only, like the plan queries):
+ * *weight_layout = 1 where a tap-major request ([Cout][R][S][Cin]) passes its checks, else 0. */
+int fi_conv2d_weight_grad_layout(const float *x, const float *dy, int N, int Cin, int H, int W, int Cout, int R, int S,
+                                 int stride_h, int stride_w, int pad_h, int pad_w, int *weight_layout);
 /* n weight gradients of ONE geometry (the identical residual blocks of a ResNet stage: 23 in C4 of ResNet-101,
  * lib/sub_module.py:103-116) in one launch: x[i], dy[i], dweight[i], dbias[i] (dbias NULL, or one pointer per problem)
  * are HOST arrays of device pointers.  A layer of the C4 stage at batch 4 is a single round of short workgroups whose
  * fixed cost (prologue, atomic epilogue) is a third of its time; n layers together take fewer, longer pixel splits
  * per layer.  Same sums as n calls of fi_conv2d_weight_grad (fp32 atomics: the order of the partial sums differs).
- * One launch needs FI_OUTPUTS_ZEROED, tap-major / 1x1 weights with Cin % 128 == 0 and a same-size stride-1 layer;
- * otherwise the call loops over the problems.  At most FI_WGRAD_BATCH_MAX problems travel in one launch.
- * _bf16 / _f16: the same on the 16-bit-operand kernels (conv_bf16_wgrad_flat_kernel; weight_layout is ignored: tap-major). */
+ * How many problems a launch carries is the per_launch that fi_conv2d_weight_grad_plan answers for these arguments (at
+ * most FI_WGRAD_BATCH_MAX; more than 1 needs FI_OUTPUTS_ZEROED among other things); with 1 the call loops over them.
+ * _bf16 / _f16: the same on the 16-bit-operand kernels (fi_conv2d_weight_grad_plan_<p>; weight_layout is ignored:
+ * tap-major). */
 #define FI_WGRAD_BATCH_MAX 24
 int fi_conv2d_weight_grad_batch(const float *const *x, const float *const *dy, float *const *dweight,
                                 float *const *dbias, int n, int N, int Cin, int H, int W, int Cout, int R, int S,
@@ -584,6 +590,31 @@ int fi_conv2d_forward_plan_f16(const float *x, const float *weight, const uint16
                                const float *scale, const float *residual, const float *gate, float *y, int N, int Cin,
                                int H, int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
                                int relu, int weight_layout, int out_h, int out_w, int output_layout, int *variant);
+/* The weight gradient of the 16-bit path (fi_conv2d_weight_grad_<p>, _db_<p>, _rows_<p>, _batch_<p>) has one host-side
+ * planner too.  Its variants, first match:
+ *   FI_WGRAD16_FLAT     3x3 / pad 1 or 1x1 / pad 0 at stride 1, H * W % 4 == 0, H * W >= 64, W >= 4, Cin % 64 == 0,
+ *                       Cout % 64 == 0, x and dy 16-byte aligned and below 2 GiB each.  The only variant that sums dbias
+ *                       itself, honours rows_live_dev and carries several problems per launch.
+ *   FI_WGRAD16_ROWS     stride_w 1 or 2, output rows of at least 4 pixels, W >= 4 * stride_w
+ *   FI_WGRAD16_GENERIC  everything else
+ * FI_NO_BF16_FLAT in the environment turns the flat variant off. */
+enum {
+    FI_WGRAD16_GENERIC = 0,          /* conv_bf16_wgrad_generic_kernel */
+    FI_WGRAD16_ROWS = 1,             /* conv_bf16_wgrad_kernel<*, *, stride_w> */
+    FI_WGRAD16_FLAT = 2              /* conv_bf16_wgrad_flat_kernel<*, *, 3x3> */
+};
+/* Which variant fi_conv2d_weight_grad_db_<p> runs for these arguments (n = 1), or the first launch of
+ * fi_conv2d_weight_grad_batch_<p> with n problems of this geometry -- x / dy / dweight being those of its first problem,
+ * dbias given for all problems or for none, every x and dy aligned like the first --, and how many of the n problems
+ * that launch carries (per_launch, may be NULL; 1 means the batch entry loops).  A host-only query like
+ * fi_conv2d_forward_plan_<p>: the planner and the argument checks of the entry itself, the same status for every argument
+ * list. */
+int fi_conv2d_weight_grad_plan_bf16(const float *x, const float *dy, float *dweight, float *dbias, int N, int Cin, int H,
+                                    int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
+                                    int flags, int n, int *variant, int *per_launch);
+int fi_conv2d_weight_grad_plan_f16(const float *x, const float *dy, float *dweight, float *dbias, int N, int Cin, int H,
+                                   int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
+                                   int flags, int n, int *variant, int *per_launch);
 int fi_conv2d_weight_grad_rows_bf16(const float *x, const float *dy, float *dweight, int N, int Cin, int H, int W,
                                     int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int flags,
                                     const int32_t *rows_live_dev, fi_stream_t stream);

@@ -5,6 +5,7 @@ rate -- the list to work down when raising the conv stack's MFMA efficiency.
 import collections
 import ctypes
 import os
+import re
 import sys
 
 import torch
@@ -54,10 +55,26 @@ class Wrapped(object):
 
     def __getattr__(self, name):
         fn = getattr(self._real, name)
-        if not name.startswith("fi_conv") or name.endswith("_eligible") or "_plan" in name:   # (host-side queries, not launches)
-            return fn
-        # the 16-bit forward entry plans its kernel: label the launch by the variant its own query names
+        if not name.startswith("fi_conv") or name.endswith("_eligible") or "_plan" in name or name.endswith("_layout"):
+            return fn                                             # (host-side queries, not launches)
+        # the 16-bit entries plan their kernel: label the launch by the variant their own query names
         query = getattr(self._real, name.replace("_live_", "_plan_")) if name.startswith("fi_conv2d_forward_live_") else None
+        wg = re.match(r"fi_conv2d_weight_grad(_db|_rows|_batch|)_(bf16|f16)$", name)
+
+        def wgrad_variant(a):
+            # the plan query's arguments (x, dy, dw, db, 11 geometry ints, flags, n) from those of the four launch entries:
+            #   _batch  (x[], dy[], dw[], db[], n, geometry, weight_layout, flags, stream)
+            #   _db     (x, dy, dw, db, geometry, flags, stream)
+            #   (none)  (x, dy, dw, geometry, flags, stream)
+            #   _rows   (x, dy, dw, geometry, flags, rows_live_dev, stream)
+            kind = wg.group(1)
+            if kind == "_batch":
+                head, geom, flags, n = [t[0] if t is not None else None for t in a[:4]], a[5:16], a[17], a[4]
+            else:
+                k = 4 if kind == "_db" else 3
+                head, geom, flags, n = list(a[:3]) + [a[3] if kind == "_db" else None], a[k:k + 11], a[k + 11], 1
+            v, per = _lib.wgrad_plan(getattr(self._real, "fi_conv2d_weight_grad_plan_" + wg.group(2)), *head, *geom, flags, n)
+            return _lib.WGRAD16_VARIANTS[v] + (" %d per launch" % per if n > 1 else "")
 
         def timed(*a):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -65,7 +82,8 @@ class Wrapped(object):
             rc = fn(*a)
             e1.record()
             ints = tuple(int(v) if isinstance(v, int) else None for v in a)
-            variant = _lib.CONV16_VARIANTS[_lib.conv16_variant(query, *a[:-2])] if query is not None else None
+            variant = _lib.CONV16_VARIANTS[_lib.conv16_variant(query, *a[:-2])] if query is not None else \
+                (wgrad_variant(a) if wg else None)
             records.append((name, ints, e0, e1, variant))
             return rc
         return timed

@@ -126,7 +126,8 @@ def _planned(query, *args):
     import ctypes
     from feature_intertwiner_amd import _lib
     k = ctypes.c_int(-1)
-    rc = query(*args, ctypes.byref(k))
+    tail = (None,) if query.__name__ == "fi_conv2d_weight_grad_plan" else ()       # its per_launch: not asked for
+    rc = query(*args, ctypes.byref(k), *tail)
     return _lib.KERNEL_KEYS[k.value] if rc == 0 else rc
 
 
@@ -171,6 +172,29 @@ def test_plan_queries_name_the_kernel_on_both_sides_of_every_threshold():
     assert wgrad(1, 6) == "conv_wgrad_bm128_1x1" and wgrad(1, 5) == "conv_wgrad_bm64_1x1"
     # what fi_conv2d_weight_grad_batch cannot put into one launch runs problem by problem: the single launch's tiles
     assert wgrad(1, 6, flags=0) == "conv_wgrad_bm64_1x1" and wgrad(1, 6, x=X + 4) == "conv_wgrad_bm64_1x1"
+
+    # ... and says so: how many of the n problems the first launch carries
+    def per_launch(N, n, flags=_lib.OUTPUTS_ZEROED, x=X):
+        return _lib.wgrad_plan(L.fi_conv2d_weight_grad_plan, x, Y, Wt, N, 1024, 64, 64, 256, 1, 1, 1, 1, 0, 0, 1, None, flags,
+                               n)[1]
+
+    assert per_launch(1, 6) == 6 and per_launch(1, 6, flags=0) == 1 and per_launch(1, 6, x=X + 4) == 1
+    assert per_launch(6, 1) == 1 and per_launch(1, 26) == _lib.WGRAD_BATCH_MAX
+
+    # fi_conv2d_weight_grad_layout: tap-major dW for whole 128-channel tiles, or 64 channels on a same-size stride-1 layer
+    # with aligned operands; a tap-major request is rejected on exactly the shapes that answer 0
+    def layout(Cin, stride=1, x=X):
+        import ctypes
+        v = ctypes.c_int(-1)
+        g = (x, Y, 2, Cin, 16, 16, 64, 3, 3, stride, stride, 1, 1)
+        assert L.fi_conv2d_weight_grad_layout(*g, ctypes.byref(v)) == 0
+        rc = _planned(L.fi_conv2d_weight_grad_plan, x, Y, Wt, *g[2:], 1, None, 0, 1)
+        assert (rc == -1 and b"weight_layout 1" in L.fi_last_error()) if v.value == 0 else isinstance(rc, str), (g, rc)
+        return v.value
+
+    assert layout(128) == 1 and layout(128, stride=2) == 1 and layout(64) == 1
+    assert layout(64, stride=2) == 0 and layout(64, x=X + 4) == 0 and layout(32) == 0
+    assert L.fi_conv2d_weight_grad_layout(X, Y, 0, 64, 16, 16, 64, 3, 3, 1, 1, 1, 1, None) == -1
 
     # the GEMM on the same tile counts (M = Cout, N = Cin, K = pixels), and its workspace: splits x M x N floats
     def gemm(M, N, K, a=X):
@@ -273,6 +297,77 @@ def test_16bit_forward_plan_names_the_variant_on_both_sides_of_every_threshold()
             v = ctypes.c_int(-1)
             assert query(*ptrs, *tail, ctypes.byref(v)) == live(*ptrs, *tail, None, None) == status, (ptrs, tail)
         assert query(X, Wt, None, None, None, None, None, Y, *ok, None) == -1
+
+
+def test_16bit_weight_grad_plan_names_the_variant_on_both_sides_of_every_threshold():
+    """fi_conv2d_weight_grad_plan_{bf16,f16} is the planner of fi_conv2d_weight_grad_db_{bf16,f16} and of the batch entry
+    run on the host: aligned fake pointer values, shapes on both sides of every threshold of the weight gradient's kernel
+    selection in csrc/conv_bf16.hip, and the number of problems a launch carries.  tests/test_gpu_wgrad16_plan.py holds
+    the launches of the same shapes to the answers named here."""
+    from feature_intertwiner_amd import _lib
+    L = _lib.load()
+    X, DY, DW, DB = 0x10000, 0x20000, 0x30000, 0x40000
+    Z = _lib.OUTPUTS_ZEROED
+
+    for sfx in ("bf16", "f16"):
+        query = getattr(L, "fi_conv2d_weight_grad_plan_" + sfx)
+        launch = getattr(L, "fi_conv2d_weight_grad_db_" + sfx)
+
+        def plan(shape, flags=0, n=1, x=X, dy=DY, db=None):
+            N, Cin, H, W, Cout, R, stride, pad = shape
+            v, per = _lib.wgrad_plan(query, x, dy, DW, db, N, Cin, H, W, Cout, R, R, stride, stride, pad, pad, flags, n)
+            return _lib.WGRAD16_VARIANTS[v], per
+
+        flat = [(1, 64, 8, 8, 64, 1, 1, 0), (1, 64, 8, 8, 64, 3, 1, 1)]
+        rows = [(1, 64, 6, 6, 64, 1, 1, 0),          # H * W = 36 < 64
+                (1, 64, 9, 9, 64, 1, 1, 0),          # H * W % 4
+                (1, 64, 8, 8, 96, 1, 1, 0),          # Cout % 64
+                (1, 96, 8, 8, 64, 1, 1, 0),          # Cin % 64
+                (1, 64, 8, 8, 64, 3, 1, 0),          # output smaller than the input
+                (1, 64, 16, 16, 64, 3, 2, 1)]        # stride 2
+        generic = [(2, 64, 3, 3, 64, 3, 1, 1),       # OW < 4
+                   (1, 64, 6, 6, 64, 3, 2, 1),       # W < 8 at stride 2
+                   (1, 64, 16, 16, 64, 3, 3, 1)]     # stride 3
+        for name, shapes in (("FLAT", flat), ("ROWS", rows), ("GENERIC", generic)):
+            for shape in shapes:
+                assert plan(shape) == (name, 1), shape
+                assert plan(shape, db=DB) == (name, 1), shape
+                # only the flat kernel carries several problems, and only into outputs the caller has cleared
+                assert plan(shape, flags=Z, n=5) == (name, 5 if name == "FLAT" else 1), shape
+        assert plan(flat[0], x=X + 4) == ("ROWS", 1) and plan(flat[0], dy=DY + 4) == ("ROWS", 1)
+        assert plan(flat[0], flags=Z, n=5, x=X + 4) == ("ROWS", 1)
+        assert _lib.WGRAD_BATCH_MAX == 24                                        # FI_WGRAD_BATCH_MAX of fi_capi.h
+        assert plan(flat[0], flags=Z, n=26) == ("FLAT", _lib.WGRAD_BATCH_MAX)
+        assert plan(flat[0], flags=0, n=5) == ("FLAT", 1)
+        assert plan(flat[0], flags=Z, n=1) == ("FLAT", 1)
+        # operands of 2 GiB: not the flat kernel, so not one launch either (the batch entry once judged this by a second
+        # copy of the predicate that had no size limit)
+        assert plan((8192, 1024, 8, 8, 64, 1, 1, 0), flags=Z, n=3) == ("ROWS", 1)
+        assert plan((8191, 1024, 8, 8, 64, 1, 1, 0), flags=Z, n=3) == ("FLAT", 3)
+
+        # an argument the launch entry rejects is rejected by the query, with the same status (and before any HIP call)
+        import ctypes
+        v, per = ctypes.c_int(-1), ctypes.c_int(-1)
+        out = (ctypes.byref(v), ctypes.byref(per))
+        g = (1, 64, 8, 8, 64, 1, 1, 1, 1, 0, 0)
+        assert query(None, DY, DW, None, *g, 0, 1, *out) == launch(None, DY, DW, None, *g, 0, None) == -1      # no x
+        assert query(X, DY, DW, None, 0, *g[1:], 0, 1, *out) == launch(X, DY, DW, None, 0, *g[1:], 0, None) == -1    # N = 0
+        # (65536 tiles of (tap, 128 input channels): a grid-size requirement, checked before the outputs are cleared)
+        big = (1, 128 * 65536, 8, 8, 64, 1, 1, 1, 1, 0, 0)
+        assert query(X, DY, DW, None, *big, 0, 1, *out) == launch(X, DY, DW, None, *big, 0, None) == -1
+        assert query(X, DY, DW, None, *g, 0, 0, *out) == -1                                                  # n = 0
+        assert query(X, DY, DW, None, *g, 0, 1, None, None) == -1
+        assert (v.value, per.value) == (-1, -1)
+
+
+def test_weight_gradient_layout_and_batching_are_stated_once():
+    """Which dW layout a weight gradient can be written in and which layers travel several to a launch is decided in
+    csrc/conv_igemm.hip and csrc/conv_bf16.hip alone: conv._conv_backward asks and restates neither."""
+    import inspect
+    from feature_intertwiner_amd import conv
+    src = inspect.getsource(conv._conv_backward)
+    for token in ("0x7fffff00", "% 16 == 0 and dz", "Cin == 64", "% 64", "(3, 3, (1, 1))"):
+        assert token not in src, token
 
 
 def test_forward_kernel_selection_of_the_16bit_path_is_stated_once():
