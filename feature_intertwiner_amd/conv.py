@@ -13,9 +13,12 @@ csrc/conv_igemm.hip:
 7x7 crops, lib/sub_module.py:707; the 7x7 conv of feat_extract on 7x7 maps, :333) are
 plain matrix products and go to the library GEMM.
 """
-import contextlib
+import collections
+import ctypes
+import os
 import weakref
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -454,168 +457,143 @@ def upsample2x(x):
         F.interpolate(x, scale_factor=2, mode='nearest')
 
 
-def _conv_backward(ctx_needs, x, w, dz, stride, padding, want_db=False, add_to_dx=None, precision=None,
-                   give_compact=False, bias_ptr=0, gate=None, w_scale=None, db_into=None, after_wgrad=None):
-    """dX and dW of z = conv(x, w) given dz (shared by the plain and the fused functions).
-    want_db: also return sum(dz) over images and pixels (the bias gradient), accumulated by the
-    weight-gradient kernel from the dY tiles it stages anyway.
-    add_to_dx: a tensor shaped like x -- or a _Compact -- that is added to dX inside the data-gradient kernel's
-    epilogue (the shortcut gradient of a bottleneck, instead of a separate add pass).
-    give_compact: a 1x1 / stride-2 layer may return dX as a _Compact (see there) instead of the full tensor.
-    gate: a tensor shaped like x; dX (with add_to_dx) is multiplied by (gate > 0) -- inside the data-gradient kernel's
-    epilogue where that kernel has one, by a separate pass otherwise.
-    w_scale [Cout]: the data gradient uses W * w_scale[co] (conv + eval-BatchNorm given the UNSCALED masked gradient:
-    _ConvBnActFn.backward); the weight gradient is the caller's to scale (after_wgrad).
-    db_into: where sum(dz) is accumulated (a zeroed [Cout] tensor) instead of the bias's arena slot.
-    after_wgrad(dw_flat, tap_major): called right after the weight-gradient launch, on the stream it ran on."""
-    L = _lib.load()
+def _data_grad(x, w, dz, stride, padding, add_to_dx=None, precision=None, give_compact=False, gate=None, w_scale=None):
+    """dX of z = conv(x, w) given dz (a tensor, or a _Compact where give_compact allows it); the arguments are
+    _conv_backward's."""
     N, Cin, H, W = x.shape
     Cout, _, R, S = w.shape
-    dx = dw = db = None
-    dz_ready = None
-    if ctx_needs[0] and ctx_needs[1] and WGRAD_SIDE_STREAM_MAX_PIXELS and \
-            N * dz.shape[2] * dz.shape[3] <= WGRAD_SIDE_STREAM_MAX_PIXELS and precision not in _LOWP:
-        # the weight gradient may run on the second stream (below): it depends on dz as it is NOW, not on the data
-        # gradient that is enqueued first
-        dz_ready = torch.cuda.Event()
-        dz_ready.record(torch.cuda.current_stream(x.device))
-    if ctx_needs[0]:
-        compact_path = stride == (2, 2) and R * S == 1 and padding == (0, 0) and Cout % 16 == 0 and Cin % 16 == 0
-        if isinstance(add_to_dx, tuple):
-            # (compact or None, full tensor or None): two gradients handed over (the projection shortcut's and the FPN
-            # lateral's); only the compact 1x1 / stride-2 path takes both inside its kernels
-            cpt, full = add_to_dx
-            if compact_path:
-                add_to_dx = (cpt, full) if (cpt is not None and full is not None) else (cpt if cpt is not None else full)
-            else:
-                parts = [t.expand() if isinstance(t, _Compact) else t for t in (cpt, full) if t is not None]
-                add_to_dx = parts[0] + parts[1] if len(parts) == 2 else (parts[0] if parts else None)
-        if isinstance(add_to_dx, _Compact) and not compact_path:
-            add_to_dx = add_to_dx.expand()
-        scaled = w_scale is not None
-        weff = None            # W * w_scale, made on demand where no cached transposed copy exists
+    # 1x1 / stride 2 (the first block of C3..C5: conv1 and the projection shortcut): the data gradient lives on the even
+    # input positions only and can travel as a _Compact
+    compact_path = stride == (2, 2) and R * S == 1 and padding == (0, 0) and Cout % 16 == 0 and Cin % 16 == 0
+    if isinstance(add_to_dx, tuple):
+        # (compact or None, full tensor or None): two gradients handed over (the projection shortcut's and the FPN
+        # lateral's); only the compact 1x1 / stride-2 path takes both inside its kernels
+        cpt, full = add_to_dx
+        if compact_path:
+            add_to_dx = (cpt, full) if (cpt is not None and full is not None) else (cpt if cpt is not None else full)
+        else:
+            parts = [t.expand() if isinstance(t, _Compact) else t for t in (cpt, full) if t is not None]
+            add_to_dx = parts[0] + parts[1] if len(parts) == 2 else (parts[0] if parts else None)
+    if isinstance(add_to_dx, _Compact) and not compact_path:
+        add_to_dx = add_to_dx.expand()
+    scaled = w_scale is not None
 
-        def w_eff():
-            return w * w_scale.view(-1, 1, 1, 1) if scaled else w
-        gate_in_kernel = gate is not None and gate.is_contiguous()
-        if stride == (1, 1):
-            if Cout % 16 == 0 and R * S <= 64:
-                # transposed weight in the kernel's tap-major layout [Cin, R, S, Cout]: re-laid-out for all
-                # layers by one launch per step (prepare_step); otherwise one copy here.  The tap flip is
-                # done by the kernel's weight indexing (weight_layout 2)
-                wt = _cached_wt(w, scaled)
-                if wt is None:
-                    wt = w_eff().permute(1, 2, 3, 0).contiguous()
-                dx = _conv_fwd(dz, wt, None, (1, 1), (R - 1 - padding[0], S - 1 - padding[1]), w_tap_major=True,
-                               flip_taps=True, residual=add_to_dx, precision=precision,
-                               gate=gate if gate_in_kernel else None)
-                add_to_dx = None
-                if gate_in_kernel:
-                    gate = None
-            else:
-                wt = w_eff().flip(2, 3).transpose(0, 1).contiguous()          # [Cin, Cout, R, S]
-                fuse = gate_in_kernel and (add_to_dx is None or torch.is_tensor(add_to_dx))
-                dx = _conv_fwd(dz, wt, None, (1, 1), (R - 1 - padding[0], S - 1 - padding[1]), precision=precision,
-                               residual=add_to_dx if fuse else None, gate=gate if fuse else None)
-                if fuse:
-                    add_to_dx = gate = None
-            if add_to_dx is not None:
-                dx = dx + add_to_dx
-        elif stride == (2, 2) and R * S == 1 and padding == (0, 0) and Cout % 16 == 0 and Cin % 16 == 0:
-            # 1x1 / stride 2 (the first block of C3..C5: conv1 and the projection shortcut): only the even input
-            # positions receive a gradient -- ONE 1x1 correlation with the cached W^T on the half-size map,
-            # a second compact gradient for the same input added in its epilogue, then one interleave pass
+    def w_eff():           # W * w_scale, made on demand where no cached transposed copy exists
+        return w * w_scale.view(-1, 1, 1, 1) if scaled else w
+    gate_in_kernel = gate is not None and gate.is_contiguous()
+    if stride == (1, 1):
+        if Cout % 16 == 0 and R * S <= 64:
+            # transposed weight in the kernel's tap-major layout [Cin, R, S, Cout]: re-laid-out for all
+            # layers by one launch per step (prepare_step); otherwise one copy here.  The tap flip is
+            # done by the kernel's weight indexing (weight_layout 2)
             wt = _cached_wt(w, scaled)
             if wt is None:
                 wt = w_eff().permute(1, 2, 3, 0).contiguous()
-            both = add_to_dx if isinstance(add_to_dx, tuple) else (add_to_dx if isinstance(add_to_dx, _Compact) else None,
-                                                                    add_to_dx if torch.is_tensor(add_to_dx) else None)
-            comp = both[0].t if both[0] is not None else None
-            c = _conv_fwd(dz, wt, None, (1, 1), (0, 0), w_tap_major=True, flip_taps=True, residual=comp,
-                          precision=precision)
-            full_add = both[1]
-            if give_compact and full_add is None and gate is None:
-                dx = _Compact(c, (H, W))
-            else:
-                dx = _interleave2({(0, 0): c}, full_add, N, Cin, H, W,
-                                  gate=gate if (gate is not None and gate.is_contiguous()) else None)
-                if gate is not None and gate.is_contiguous():
-                    gate = None
+            dx = _conv_fwd(dz, wt, None, (1, 1), (R - 1 - padding[0], S - 1 - padding[1]), w_tap_major=True,
+                           flip_taps=True, residual=add_to_dx, precision=precision,
+                           gate=gate if gate_in_kernel else None)
+            add_to_dx = None
+            if gate_in_kernel:
+                gate = None
         else:
-            dx = _strided_dgrad(dz, w_eff(), (H, W), stride, padding, precision, add=add_to_dx)
-        if gate is not None:
-            if isinstance(dx, _Compact):
-                dx = dx.expand()
-            dx = _relu_mask(dx, gate.contiguous(), dx)
-    if ctx_needs[1]:
-        geom = (N, Cin, H, W, Cout, R, S, stride[0], stride[1], padding[0], padding[1])
-        # bf16 weight gradient: always tap-major, so the parameter must be stored that way (or be 1x1)
-        bf16 = precision in _LOWP and (R * S == 1 or (Cin % 16 == 0 and w.is_contiguous(memory_format=torch.channels_last)))
-        # tap-major dW ([Cout,R,S,Cin]) wherever the fp32 kernels can write it: the library says
-        hwc = 1 if bf16 else _lib.wgrad_tap_major(_lib.ptr(x), _lib.ptr(dz), *geom)
-        shape = (Cout, R, S, Cin) if (hwc and R * S > 1) else (Cout, Cin, R, S)
-        # pre-zeroed slice of the step's gradient arena (one fill per step instead of one per layer); a repeated
-        # use of the layer accumulates into the same slice.  (With want_db the kernel clears dW and db itself.)
-        # With want_db the fp32 kernel accumulates the bias gradient too: both outputs must be pre-zeroed slots, or
-        # the kernel clears both itself.
-        db_slot = None
-        if want_db:
-            if db_into is not None:
-                db_slot = db_into
-            else:
-                db_slot, _ = _arena_take(("db", bias_ptr), Cout) if bias_ptr else (None, False)
-        if want_db and db_slot is None:
-            dw, first = None, False
+            wt = w_eff().flip(2, 3).transpose(0, 1).contiguous()          # [Cin, Cout, R, S]
+            fuse = gate_in_kernel and (add_to_dx is None or torch.is_tensor(add_to_dx))
+            dx = _conv_fwd(dz, wt, None, (1, 1), (R - 1 - padding[0], S - 1 - padding[1]), precision=precision,
+                           residual=add_to_dx if fuse else None, gate=gate if fuse else None)
+            if fuse:
+                add_to_dx = gate = None
+        if add_to_dx is not None:
+            dx = dx + add_to_dx
+    elif compact_path:
+        # only the even input positions receive a gradient -- ONE 1x1 correlation with the cached W^T on the half-size
+        # map, a second compact gradient for the same input added in its epilogue, then one interleave pass
+        wt = _cached_wt(w, scaled)
+        if wt is None:
+            wt = w_eff().permute(1, 2, 3, 0).contiguous()
+        both = add_to_dx if isinstance(add_to_dx, tuple) else (add_to_dx if isinstance(add_to_dx, _Compact) else None,
+                                                                add_to_dx if torch.is_tensor(add_to_dx) else None)
+        comp = both[0].t if both[0] is not None else None
+        c = _conv_fwd(dz, wt, None, (1, 1), (0, 0), w_tap_major=True, flip_taps=True, residual=comp,
+                      precision=precision)
+        full_add = both[1]
+        if give_compact and full_add is None and gate is None:
+            return _Compact(c, (H, W))
+        dx = _interleave2({(0, 0): c}, full_add, N, Cin, H, W, gate=gate if gate_in_kernel else None)
+        if gate_in_kernel:
+            gate = None
+    else:
+        dx = _strided_dgrad(dz, w_eff(), (H, W), stride, padding, precision, add=add_to_dx)
+    if gate is not None:
+        dx = _relu_mask(dx, gate.contiguous(), dx)
+    return dx
+
+
+def _weight_grad(x, w, dz, stride, padding, want_db=False, precision=None, bias_ptr=0, db_into=None, after_wgrad=None):
+    """(dW, db) of z = conv(x, w) given dz, launched at once or queued for a launch together with other layers of the
+    same geometry (_defer_wgrad); the arguments are _conv_backward's.  dW is None where it was accumulated into the slot
+    autograd already holds (a repeated use of the layer), and so is db."""
+    L = _lib.load()
+    N, Cin, H, W = x.shape
+    Cout, _, R, S = w.shape
+    db = None
+    geom = (N, Cin, H, W, Cout, R, S, stride[0], stride[1], padding[0], padding[1])
+    # bf16 weight gradient: always tap-major, so the parameter must be stored that way (or be 1x1)
+    bf16 = precision in _LOWP and (R * S == 1 or (Cin % 16 == 0 and w.is_contiguous(memory_format=torch.channels_last)))
+    # tap-major dW ([Cout,R,S,Cin]) wherever the fp32 kernels can write it: the library says
+    hwc = 1 if bf16 else _lib.wgrad_tap_major(_lib.ptr(x), _lib.ptr(dz), *geom)
+    tap_major = bool(hwc and R * S > 1)            # (the 16-bit kernels write tap-major: hwc is set)
+    shape = (Cout, R, S, Cin) if tap_major else (Cout, Cin, R, S)
+    # pre-zeroed slice of the step's gradient arena (one fill per step instead of one per layer); a repeated
+    # use of the layer accumulates into the same slice.  (With want_db the kernel clears dW and db itself.)
+    # With want_db the fp32 kernel accumulates the bias gradient too: both outputs must be pre-zeroed slots, or
+    # the kernel clears both itself.
+    db_slot = None
+    if want_db:
+        if db_into is not None:
+            db_slot = db_into
         else:
-            dw, first = _arena_take(("dw", w.data_ptr()), Cout * Cin * R * S)
-            if dw is None:
-                db_slot = None
-            elif after_wgrad is not None and not first:
-                # a repeated use of the layer would add unscaled sums onto the scaled ones of the first use:
-                # _ConvBnActFn.backward routes repeated uses to the path that has no after_wgrad
-                raise _lib.FiError("after_wgrad on a layer applied more than once per step")
-        flags = _lib.OUTPUTS_ZEROED if dw is not None else 0
-        dw = dw.view(shape) if dw is not None else torch.empty(shape, device=x.device, dtype=torch.float32)
-        hand_over = first or not flags
-        if want_db:
-            db = db_slot if db_slot is not None else torch.empty(Cout, device=x.device, dtype=torch.float32)
-        side = None
-        # second stream only if autograd will ADOPT dw as the parameter's gradient: a dw whose memory order differs
-        # from the parameter's is cloned by AccumulateGrad, on the main stream, while the kernel may still be running
-        adopt = R * S == 1 or bool(hwc) == (not w.is_contiguous())
-        if flags and dz_ready is not None and not bf16 and adopt:
-            main = torch.cuda.current_stream(x.device)
-            side = _wgrad_side_stream(x.device)
-            side.wait_event(dz_ready)                      # dz (and x) were complete on the main stream there
-            x.record_stream(side)
-            dz.record_stream(side)
-        if flags and not first and _WGQ["queues"]:
-            # a further use of a layer in this backward pass (two forward passes before one backward; the dense RPN on five
-            # levels): its first use may still be queued together with the pass that scales dW in place -- run the queue
-            # before this use adds to the slot, and do not queue this one
-            flush_deferred_wgrads()
-        # queued for a launch together with the other layers of its geometry (_flush_wgrads): where the library would put
-        # several such problems into one launch
-        deferred = False
-        if flags and first and adopt and WGRAD_BATCH > 1 and N * dz.shape[2] * dz.shape[3] <= WGRAD_BATCH_MAX_PIXELS and \
-                Cin % 128 == 0:         # policy: batching was only measured on the C3-C5 blocks (profiles/r04_ab_wgrad_*.txt)
-            nq = min(WGRAD_BATCH, _lib.WGRAD_BATCH_MAX)
+            db_slot, _ = _arena_take(("db", bias_ptr), Cout) if bias_ptr else (None, False)
+    if want_db and db_slot is None:
+        dw, first = None, False
+    else:
+        dw, first = _arena_take(("dw", w.data_ptr()), Cout * Cin * R * S)
+        if dw is None:
+            db_slot = None
+        elif after_wgrad is not None and not first:
+            # a repeated use of the layer would add unscaled sums onto the scaled ones of the first use:
+            # _ConvBnActFn.backward routes repeated uses to the path that has no after_wgrad
+            raise _lib.FiError("after_wgrad on a layer applied more than once per step")
+    flags = _lib.OUTPUTS_ZEROED if dw is not None else 0
+    dw = dw.view(shape) if dw is not None else torch.empty(shape, device=x.device, dtype=torch.float32)
+    hand_over = first or not flags
+    if want_db:
+        db = db_slot if db_slot is not None else torch.empty(Cout, device=x.device, dtype=torch.float32)
+    # deferral only if autograd will ADOPT dw as the parameter's gradient: a queued kernel writes dw after AccumulateGrad
+    # has run, and a dw whose memory order differs from the parameter's is cloned there -- the clone would stay empty
+    adopt = R * S == 1 or bool(hwc) == (not w.is_contiguous())
+    if flags and not first and _WGQ["queues"]:
+        # a further use of a layer in this backward pass (two forward passes before one backward; the dense RPN on five
+        # levels): its first use may still be queued together with the pass that scales dW in place -- run the queue
+        # before this use adds to the slot, and do not queue this one
+        flush_deferred_wgrads()
+    # queued for a launch together with the other layers of its geometry (_flush_wgrads): where the library would put
+    # several such problems into one launch
+    deferred = False
+    if flags and first and adopt and WGRAD_BATCH > 1 and N * dz.shape[2] * dz.shape[3] <= WGRAD_BATCH_MAX_PIXELS and \
+            Cin % 128 == 0:         # policy: batching was only measured on the C3-C5 blocks (profiles/r04_ab_wgrad_*.txt)
+        nq = min(WGRAD_BATCH, _lib.WGRAD_BATCH_MAX)
+        if bf16:
+            per = _lib.wgrad_plan(_lowp_fn(L, "conv2d_weight_grad_plan", precision), _lib.ptr(x), _lib.ptr(dz),
+                                  _lib.ptr(dw), _lib.ptr(db), *geom, flags, nq)[1]
+        else:
+            per = _lib.wgrad_plan(L.fi_conv2d_weight_grad_plan, _lib.ptr(x), _lib.ptr(dz), _lib.ptr(dw), *geom, hwc,
+                                  _lib.ptr(db), flags, nq)[1]
+        deferred = per > 1 and _defer_wgrad(
+            (N, Cin, H, W, Cout, R, S, padding, want_db and db is not None, precision if bf16 else None),
+            x, dz, dw, db if want_db else None, after_wgrad, tap_major)
+    if not deferred:
+        with torch.cuda.device(x.device):
             if bf16:
-                per = _lib.wgrad_plan(_lowp_fn(L, "conv2d_weight_grad_plan", precision), _lib.ptr(x), _lib.ptr(dz),
-                                      _lib.ptr(dw), _lib.ptr(db), *geom, flags, nq)[1]
-            else:
-                per = _lib.wgrad_plan(L.fi_conv2d_weight_grad_plan, _lib.ptr(x), _lib.ptr(dz), _lib.ptr(dw), *geom, hwc,
-                                      _lib.ptr(db), flags, nq)[1]
-            deferred = per > 1 and _defer_wgrad(
-                (N, Cin, H, W, Cout, R, S, padding, want_db and db is not None, precision if bf16 else None),
-                x, dz, dw, db if want_db else None, after_wgrad, bool(hwc and R * S > 1), dz_ready,
-                torch.cuda.current_stream(x.device), side)
-            if deferred:
-                side = None
-        with torch.cuda.device(x.device), (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-            if deferred:
-                pass
-            elif bf16:
                 _log_flops("conv_bf16_wgrad", 2 * N * Cout * dz.shape[2] * dz.shape[3] * Cin * R * S)
                 _lib.check(_lowp_fn(L, "conv2d_weight_grad_db", precision)(_lib.ptr(x), _lib.ptr(dz), _lib.ptr(dw), _lib.ptr(db),
                                                                            *geom, flags, _lib.current_stream()),
@@ -626,80 +604,67 @@ def _conv_backward(ctx_needs, x, w, dz, stride, padding, want_db=False, add_to_d
                     _log_flops(_lib.KERNEL_KEYS[_lib.wgrad_plan(L.fi_conv2d_weight_grad_plan, *args[:-1], 1)[0]],
                                2 * N * Cout * dz.shape[2] * dz.shape[3] * Cin * R * S)
                 _lib.check(L.fi_conv2d_weight_grad(*args), "fi_conv2d_weight_grad")
-            if after_wgrad is not None and not deferred:
-                after_wgrad(dw, db, bool(hwc and R * S > 1))        # (the 16-bit kernels write tap-major: hwc is set)
-        if side is not None:
-            _queue_wgrad_join(main, side)
-        _age_wgrad_queues()
-        if hwc and R * S > 1:
-            dw = dw.permute(0, 3, 1, 2)
-        if not hand_over:
-            dw = None                 # accumulated into the slot autograd already holds
-            if want_db:
-                db = None
+            if after_wgrad is not None:
+                after_wgrad(dw, db, tap_major)
+    _age_wgrad_queues()
+    if tap_major:
+        dw = dw.permute(0, 3, 1, 2)
+    # (not handed over: accumulated into the slot autograd already holds)
+    return (dw, db) if hand_over else (None, None)
+
+
+def _conv_backward(ctx_needs, x, w, dz, stride, padding, want_db=False, add_to_dx=None, precision=None,
+                   give_compact=False, bias_ptr=0, gate=None, w_scale=None, db_into=None, after_wgrad=None):
+    """dX and dW of z = conv(x, w) given dz (shared by the plain and the fused functions): two independent halves that
+    both read dz, the data gradient enqueued first.
+    want_db: also return sum(dz) over images and pixels (the bias gradient), accumulated by the
+    weight-gradient kernel from the dY tiles it stages anyway.
+    add_to_dx: a tensor shaped like x -- or a _Compact -- that is added to dX inside the data-gradient kernel's
+    epilogue (the shortcut gradient of a bottleneck, instead of a separate add pass).
+    give_compact: a 1x1 / stride-2 layer may return dX as a _Compact (see there) instead of the full tensor.
+    gate: a tensor shaped like x; dX (with add_to_dx) is multiplied by (gate > 0) -- inside the data-gradient kernel's
+    epilogue where that kernel has one, by a separate pass otherwise.
+    w_scale [Cout]: the data gradient uses W * w_scale[co] (conv + eval-BatchNorm given the UNSCALED masked gradient:
+    _ConvBnActFn.backward); the weight gradient is the caller's to scale (after_wgrad).
+    db_into: where sum(dz) is accumulated (a zeroed [Cout] tensor) instead of the bias's arena slot.
+    after_wgrad(dw, db, tap_major): called right after the weight-gradient launch, on the stream that is current then
+    (for a queued layer: at the flush)."""
+    dx = dw = db = None
+    if ctx_needs[0]:
+        dx = _data_grad(x, w, dz, stride, padding, add_to_dx, precision, give_compact, gate, w_scale)
+    if ctx_needs[1]:
+        dw, db = _weight_grad(x, w, dz, stride, padding, want_db, precision, bias_ptr, db_into, after_wgrad)
     elif want_db:
         db = dz.sum((0, 2, 3))
     return (dx, dw, db) if want_db else (dx, dw)
 
 
-# ---- weight gradients of small layers on a second stream ---------------------------------------------------------
-# The data gradient and the weight gradient of a layer are independent (both read dz).  For layers whose grids are a
-# single round of workgroups (the C3..C5 stages at batch 4) each kernel leaves the chip part-empty while its
-# workgroups start up and while they drain (prologue, short K loops, atomic epilogue); issued on two streams the
-# tail of one kernel overlaps the head of the other.  Only for gradients that land in the persistent arena (no
-# allocator involvement); the main stream re-joins at the end of the backward pass (an autograd engine callback) and
-# data_parallel.GradientBuckets waits for this stream before it reduces a bucket.  Measured in one box (scripts/ab_env.sh):
-# fp32 step 157.9 -> 155.1 ms with every layer on the second stream (155.3 with only layers <= 65 536 pixels); the
-# 16-bit kernels are bound by operand traffic through L2, not by their tails -- there it costs 0.5-1 ms and stays off.
-import os as _os
-# Round 4: OFF by default.  With the weight gradients of a stage's identical layers batched into few long launches
-# (WGRAD_BATCH below) their tails no longer need hiding, and two MFMA-bound kernels sharing the chip only slow each other:
-# same-box A/B 112.7 (second stream) vs 110.9 ms/step (main stream), profiles/r04_ab_wgrad_stream.txt.
-WGRAD_SIDE_STREAM_MAX_PIXELS = int(_os.environ.get("FI_WGRAD_SIDE_PIXELS", "0"))   # largest layer (pixels) that takes the second stream; 0 disables
-_WG_STREAM = {}
-def wgrad_stream(device):
-    """The second stream weight gradients may run on (None before first use)."""
-    return _WG_STREAM.get(_lib.device_key(device))
-
-
-def _wgrad_side_stream(dev):
-    key = _lib.device_key(dev)
-    st = _WG_STREAM.get(key)
-    if st is None:
-        st = _WG_STREAM[key] = torch.cuda.Stream(device=dev)
-    return st
-
-
-def _queue_wgrad_join(main, side):
-    """Make `main` (the stream the layer's backward runs on) and the stream backward() was called from wait for the
-    weight gradients on `side` when the running backward pass ends.  One engine callback per launch: a stream wait is
-    a few microseconds of host time, and no state survives a backward pass that raises."""
-    def join():
-        main.wait_stream(side)
-        torch.cuda.current_stream(side.device).wait_stream(side)
-    try:
-        torch.autograd.Variable._execution_engine.queue_callback(join)
-    except RuntimeError:          # not inside a backward pass: join right away
-        join()
-
-
 # ---- weight gradients of identical layers in ONE launch ---------------------------------------------------------------
+# The data gradient and the weight gradient of a layer are independent (both read dz) and run one after the other on the
+# main stream.  (A variant that put the weight gradients on a second stream was measured slower once they were batched
+# and was removed: profiles/r04_ab_wgrad_stream.txt.)
 # A layer of the C4 stage at batch 4 ([4, 256|1024, 64, 64]) gives the weight-gradient kernel 16..36 tiles: to fill the
 # chip it is cut into up to 64 pixel splits, one round of short workgroups whose fixed cost -- prologue, atomic epilogue of
 # 64 KB per workgroup -- is a third of the launch (86..95 us for 8.6 GFLOP whatever the shape; scripts/wg_batch_probe.py:
 # the same arithmetic with 4x / 23x the pixels per launch runs at 123 / 130 TFLOP/s instead of 90..98).  ResNet-101 has 23
-# such blocks in a row.  Their weight gradients already run on the second stream and nothing reads them before the
-# optimiser, so they are QUEUED per geometry and launched WGRAD_BATCH at a time (fi_conv2d_weight_grad_batch: the operand
-# pointers travel in the kernel arguments), each problem with fewer, longer splits.  A queue is also flushed when its
-# geometry has not been seen for WGRAD_BATCH_AGE convolution backward calls (the stage is over), when a data-parallel
-# bucket is about to be reduced (data_parallel.GradientBuckets), and at the end of the backward pass.
-WGRAD_BATCH = int(_os.environ.get("FI_WGRAD_BATCH", "12"))              # problems per launch; <= 1 disables the queue
+# such blocks in a row.  Nothing reads their weight gradients before the optimiser, so they are QUEUED per geometry and
+# launched WGRAD_BATCH at a time (fi_conv2d_weight_grad_batch: the operand pointers travel in the kernel arguments), each
+# problem with fewer, longer splits.  A queue is flushed when it is full, when its geometry has not been seen for
+# WGRAD_BATCH_AGE convolution backward calls (the stage is over), when a layer is used again in the same backward pass
+# (_weight_grad), when a data-parallel bucket is about to be reduced
+# (data_parallel.GradientBuckets), and at the end of the backward pass.
+WGRAD_SIDE_STREAM_MAX_PIXELS = 0          # inert: bench.py saves, zeroes and restores it around its profiled passes
+WGRAD_BATCH = int(os.environ.get("FI_WGRAD_BATCH", "12"))               # problems per launch; <= 1 disables the queue
 WGRAD_BATCH_AGE = 9
 WGRAD_BATCH_MAX_PIXELS = 65536                                         # larger layers fill the chip on their own
-_WGQ = {"queues": {}, "tick": 0, "armed": False, "streams": {}}
+_WGQ = {"queues": {}, "tick": 0, "armed": False}
+_QueuedWgrad = collections.namedtuple("_QueuedWgrad", "x dz dw db after tap_major")
+# what a batched flush needs to run the fi_bn_fold_grad passes of n queued layers as one launch: the `fold` attribute of
+# an after_wgrad callback (_ConvBnActFn._backward_unscaled)
+_BnFold = collections.namedtuple("_BnFold", "w scale mean var eps bias dgamma dbias sums")
 
 
-def _defer_wgrad(key, x, dz, dw, db, after, tap_major, ev, main, side):
+def _defer_wgrad(key, x, dz, dw, db, after, tap_major):
     """Queue one weight gradient (True), or decline (False: not inside a backward pass -- nobody would flush)."""
     q = _WGQ
     if not q["armed"]:
@@ -708,12 +673,10 @@ def _defer_wgrad(key, x, dz, dw, db, after, tap_major, ev, main, side):
         except RuntimeError:
             return False
         q["armed"] = True
-    if side is not None:
-        q["streams"][(id(main), id(side))] = (main, side)
-    e = q["queues"].setdefault(key, {"items": [], "last": 0, "main": main, "side": side})
+    e = q["queues"].setdefault(key, {"items": [], "last": 0})
     # (an alias of dw: AccumulateGrad adopts a gradient only while nobody else holds the tensor it was handed -- a second
     # reference to that very object makes it clone the still-empty slot)
-    e["items"].append((x, dz, dw.view(dw.shape), None if db is None else db.view(db.shape), after, tap_major, ev))
+    e["items"].append(_QueuedWgrad(x, dz, dw.view(dw.shape), None if db is None else db.view(db.shape), after, tap_major))
     e["last"] = q["tick"]
     if len(e["items"]) >= min(WGRAD_BATCH, _lib.WGRAD_BATCH_MAX):
         _flush_wgrads(key)
@@ -729,67 +692,58 @@ def _age_wgrad_queues():
 
 
 def _flush_wgrads(key):
-    import ctypes
     e = _WGQ["queues"].pop(key, None)
     if not e or not e["items"]:
         return
-    items, side = e["items"], e["side"]
+    items = e["items"]
     N, Cin, H, W, Cout, R, S, padding, has_db, lowp = key
     n = len(items)
     L = _lib.load()
     arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
-    xs, dzs, dws = [it[0] for it in items], [it[1] for it in items], [it[2] for it in items]
-    if side is not None:                   # (None: no second stream for weight gradients -- launched where we are)
-        side.wait_event(items[-1][6])      # the events were recorded on one stream, in order: the last covers all
-        for t in xs + dzs:
-            t.record_stream(side)
-    with torch.cuda.device(xs[0].device), (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
+    xs, dzs, dws, dbs = ([getattr(it, k) for it in items] for k in ("x", "dz", "dw", "db"))
+    with torch.cuda.device(xs[0].device):
         geom = (N, Cin, H, W, Cout, R, S, 1, 1, padding[0], padding[1], 1)
         if lowp:
             _log_flops("conv_bf16_wgrad", 2.0 * n * N * H * W * Cout * Cin * R * S)
         elif FLOP_LOG is not None:         # (the batch entry takes pointer tables: the query gets the first problem and n)
             _log_flops(_lib.KERNEL_KEYS[_lib.wgrad_plan(L.fi_conv2d_weight_grad_plan, _lib.ptr(xs[0]), _lib.ptr(dzs[0]),
-                                                        _lib.ptr(dws[0]), *geom, _lib.ptr(items[0][3]) if has_db else None,
+                                                        _lib.ptr(dws[0]), *geom, _lib.ptr(dbs[0]) if has_db else None,
                                                         _lib.OUTPUTS_ZEROED, n)[0]],
                        2.0 * n * N * H * W * Cout * Cin * R * S)
         fn = _lowp_fn(L, "conv2d_weight_grad_batch", lowp) if lowp else L.fi_conv2d_weight_grad_batch
-        _lib.check(fn(arr(xs), arr(dzs), arr(dws), arr([it[3] for it in items]) if has_db else None, n, *geom,
+        _lib.check(fn(arr(xs), arr(dzs), arr(dws), arr(dbs) if has_db else None, n, *geom,
                       _lib.OUTPUTS_ZEROED, _lib.current_stream()), "fi_conv2d_weight_grad_batch")
-        folds = [getattr(it[4], "fold", None) for it in items]
-        if n > 1 and all(f is not None for f in folds) and len({(f[4], f[5] is None, f[6] is None, f[7] is None,
-                                                                 f[0].is_contiguous()) for f in folds}) == 1:
+        folds = [getattr(it.after, "fold", None) for it in items]
+        if n > 1 and all(f is not None for f in folds) and \
+                len({(f.eps, f.bias is None, f.dgamma is None, f.dbias is None, f.w.is_contiguous()) for f in folds}) == 1:
             # every layer of the batch is conv + eval-BatchNorm: their fi_bn_fold_grad passes as one launch too
             f0 = folds[0]
-            w_tap_major = R * S > 1 and not f0[0].is_contiguous()
-            here = torch.cuda.current_stream(xs[0].device)
+            w_tap_major = R * S > 1 and not f0.w.is_contiguous()
+            here = torch.cuda.current_stream(xs[0].device)      # the flush runs on whatever stream is current now
             for f in folds:
-                f[8].record_stream(here)
-                f[1].record_stream(here)
-            col = lambda k: arr([f[k] for f in folds]) if f0[k] is not None else None
-            _lib.check(L.fi_bn_fold_grad_batch(arr(dws), col(0), arr([it[3] for it in items]), col(1), col(2), col(3), f0[4],
-                                               col(5), col(6), col(7), n, Cout, Cin, R * S, 1 if items[0][5] else 0,
-                                               1 if w_tap_major else 0, _lib.current_stream()), "fi_bn_fold_grad_batch")
+                f.sums.record_stream(here)
+                f.scale.record_stream(here)
+            col = lambda k: arr([getattr(f, k) for f in folds]) if getattr(f0, k) is not None else None
+            _lib.check(L.fi_bn_fold_grad_batch(arr(dws), col("w"), arr(dbs), col("scale"), col("mean"), col("var"), f0.eps,
+                                               col("bias"), col("dgamma"), col("dbias"), n, Cout, Cin, R * S,
+                                               1 if items[0].tap_major else 0, 1 if w_tap_major else 0,
+                                               _lib.current_stream()), "fi_bn_fold_grad_batch")
         else:
-            for x, dz, dw, db, after, tap_major, ev in items:
-                if after is not None:
-                    after(dw, db, tap_major)
+            for it in items:
+                if it.after is not None:
+                    it.after(it.dw, it.db, it.tap_major)
 
 
 def flush_deferred_wgrads():
-    """Launch every queued weight gradient now (on the weight-gradient stream)."""
+    """Launch every queued weight gradient now, on the current stream."""
     for key in list(_WGQ["queues"].keys()):
         _flush_wgrads(key)
 
 
 def _finish_wgrads():
-    """Engine callback at the end of the backward pass that queued something: flush, then re-join the streams."""
-    q = _WGQ
-    q["armed"] = False
+    """Engine callback at the end of the backward pass that queued something: flush what is left."""
+    _WGQ["armed"] = False
     flush_deferred_wgrads()
-    joins, q["streams"] = list(q["streams"].values()), {}
-    for main, side in joins:
-        main.wait_stream(side)
-        torch.cuda.current_stream(side.device).wait_stream(side)
 
 
 # ---- per-step derived state: W^T for the data gradient, zeroed gradient arena ---------------------
@@ -849,9 +803,8 @@ def _arena_take(key, numel, partner=None):
     return _ARENA["buf"][slot[0]:slot[0] + numel], first
 
 
-import numpy as _np
-_TR_DESC = _np.dtype([("src", "<u8"), ("dst", "<u8"), ("rows", "<i4"), ("cols", "<i4"), ("taps", "<i4"), ("pad", "<i4"),
-                      ("tile_base", "<i8"), ("row_scale", "<u8")])      # FiTransposeDesc
+_TR_DESC = np.dtype([("src", "<u8"), ("dst", "<u8"), ("rows", "<i4"), ("cols", "<i4"), ("taps", "<i4"), ("pad", "<i4"),
+                     ("tile_base", "<i8"), ("row_scale", "<u8")])      # FiTransposeDesc
 
 
 def invalidate_step_state():
@@ -886,7 +839,6 @@ def _prepare_step(model, grad_on):
     if _WGQ["queues"] or _WGQ["armed"]:
         # leftovers of a backward pass that raised before its end-of-pass callback ran: their slots are about to be cleared
         _WGQ["queues"].clear()
-        _WGQ["streams"].clear()
         _WGQ["armed"] = False
     if len(_WB) > 4096:
         # bf16 copies of weights that were temporaries (the deconv's reshaped weight, transposes made on the fly)
@@ -911,7 +863,6 @@ def _prepare_step(model, grad_on):
         tr = [m for m in convs if (tuple(m.stride) == (1, 1) or m.weight.shape[2] * m.weight.shape[3] == 1) and
               m.weight.shape[0] % 16 == 0 and
               m.weight.shape[1] % 16 == 0 and m.weight.shape[2] * m.weight.shape[3] <= 64 and m.weight.requires_grad]
-        import numpy as np
         desc = np.zeros(len(tr), dtype=_TR_DESC)
         wts, base = [], 0
         for i, m in enumerate(tr):
@@ -977,7 +928,7 @@ def _prepare_step(model, grad_on):
     if plan["table"] is not None and plan["scales"] != sig:
         desc = plan["desc"]
         desc["row_scale"] = sig
-        plan["table"] = torch.from_numpy(desc.view(_np.uint8).copy()).to(dev)
+        plan["table"] = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
         plan["scales"] = sig
         plan["versions"] = None
     versions = tuple(m.weight._version for m in plan["tr"]) + tuple(b._fi_fold[2] for b in scales if b is not None)
@@ -1038,7 +989,7 @@ def _prepare_step(model, grad_on):
         _ARENA["buf"] = None
 
 
-_UNSCALED_BACKWARD = not _os.environ.get("FI_BN_BWD_OLD")      # A/B switch (scripts/ab_env.sh)
+_UNSCALED_BACKWARD = not os.environ.get("FI_BN_BWD_OLD")      # A/B switch (scripts/ab_env.sh)
 # Gates and the FPN-lateral hand-off on / off.  Off + _UNSCALED_BACKWARD off = the round-2 form of the backward pass, kept
 # as the differential reference of tests/test_gpu_detector.py::test_detector_gradients_agree_between_backward_forms
 GATES = True
@@ -1161,7 +1112,7 @@ class _ConvBnActFn(torch.autograd.Function):
             Cin, R, S = w.shape[1], w.shape[2], w.shape[3]
             w_tap_major = R * S > 1 and not w.is_contiguous()       # _dense(): contiguous or channels-last
             out["s"] = s
-            here = torch.cuda.current_stream(sums.device)                  # the weight gradient's stream
+            here = torch.cuda.current_stream(sums.device)       # (a deferred flush runs on the stream current THEN)
             sums.record_stream(here)
             scale.record_stream(here)       # folded in-layer (first step, no prepare_step): a temporary of the forward
             _lib.check(L.fi_bn_fold_grad(_lib.ptr(dw_flat), _lib.ptr(w), _lib.ptr(s), _lib.ptr(scale), _lib.ptr(mean),
@@ -1171,8 +1122,8 @@ class _ConvBnActFn(torch.autograd.Function):
                                          1 if tap_major else 0, 1 if w_tap_major else 0, _lib.current_stream()),
                        "fi_bn_fold_grad")
         # what a batched flush needs to run the folds of n queued layers as ONE launch (_flush_wgrads)
-        finish.fold = (w, scale, mean, var, float(eps), b if has_bias else None, sums[C:2 * C] if want_gamma else None,
-                       sums[2 * C:] if want_db else None, sums)
+        finish.fold = _BnFold(w, scale, mean, var, float(eps), b if has_bias else None,
+                              sums[C:2 * C] if want_gamma else None, sums[2 * C:] if want_db else None, sums)
         dx, dw, _ = _conv_backward(ctx.needs_input_grad, x, w, g, stride, padding, want_db=True, add_to_dx=add,
                                    precision=ctx.precision, give_compact=ctx.dx_give_to is not None,
                                    gate=x if ctx.dx_gate else None, w_scale=scale, db_into=sums[:C],
@@ -1365,7 +1316,6 @@ def refresh_bn_folds():
             keys.append(fk)
     if not pairs:
         return
-    import numpy as np
     L = _lib.load()
     dev = pairs[0][1].weight.device
     key = tuple((id(b), fk[-1]) for (_, b), fk in zip(pairs, keys))
@@ -1414,7 +1364,7 @@ def _invalidate_bn_folds(module=None):
             m._fi_fold = None
 
 
-FUSED_FC = _os.environ.get("FI_FUSED_FC", "1") != "0"       # A/B switch: linear_bn_act vs conv, affine, ReLU as torch ops
+FUSED_FC = os.environ.get("FI_FUSED_FC", "1") != "0"       # A/B switch: linear_bn_act vs conv, affine, ReLU as torch ops
 
 
 def conv_bn_act(x, conv, bn, relu=True, residual=None, channels_last_out=False, res_grad_to=None,

@@ -21,11 +21,6 @@ import torch.distributed as dist
 from . import grad_arena
 
 
-def conv_wgrad_stream(device):
-    from .conv import wgrad_stream          # (conv imports nothing from here; late import keeps CPU-only use light)
-    return wgrad_stream(device)
-
-
 class _AllReduceSumIdentityGrad(torch.autograd.Function):
     """y = sum over ranks of x; backward returns world_size * g.
 
@@ -332,9 +327,6 @@ class GradientBuckets(object):
                 self.comm_stream.wait_stream(torch.cuda.current_stream(self.device))
                 for s in self._grad_streams[bi]:           # gradients produced on other streams (see _reset)
                     self.comm_stream.wait_stream(s)
-                wg = conv_wgrad_stream(self.device)        # weight gradients on their own stream (conv.WGRAD_SIDE_STREAM...)
-                if wg is not None:
-                    self.comm_stream.wait_stream(wg)
                 with torch.cuda.stream(self.comm_stream):
                     ev = None
                     if self.profile is not None and self.stream_ordered:

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of a Python-level switch inside ONE box call: bench twice each way, interleaved.
-#   bash scripts/ab_env.sh "FI_WGRAD_SIDE=0" "FI_WGRAD_SIDE=1" [bench args...]
+#   bash scripts/ab_env.sh "FI_WGRAD_BATCH=1" "FI_WGRAD_BATCH=12" [bench args...]
 A="$1"; B="$2"; shift 2
 for i in 1 2; do
   for v in "$A" "$B"; do

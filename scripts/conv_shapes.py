@@ -12,11 +12,10 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+# every side stream off, so that the events bracket the kernel (round 5's file had three GEMMs of the OT module's
+# backward at 0.1-0.9 TFLOP/s: 8 workgroups of the meta loss on the THIRD stream waiting for CU slots next to a
+# main-stream convolution -- the events bracketed the wait, not the kernel)
 os.environ.setdefault("FI_DEAD_SIDE", "0")
-os.environ.setdefault("FI_WGRAD_SIDE_PIXELS", "0")      # weight gradients on the main stream: the events bracket the kernel
-# ... and so is every other side stream (round 5's file had three GEMMs of the OT module's backward at 0.1-0.9 TFLOP/s: 8
-# workgroups of the meta loss on the THIRD stream waiting for CU slots next to a main-stream convolution -- the events
-# bracketed the wait, not the kernel)
 os.environ.setdefault("FI_META_SIDE", "0")
 os.environ.setdefault("FI_BIG_SIDE", "0")
 os.environ.setdefault("FI_PROPOSAL_SIDE", "0")

@@ -362,12 +362,23 @@ def test_16bit_weight_grad_plan_names_the_variant_on_both_sides_of_every_thresho
 
 def test_weight_gradient_layout_and_batching_are_stated_once():
     """Which dW layout a weight gradient can be written in and which layers travel several to a launch is decided in
-    csrc/conv_igemm.hip and csrc/conv_bf16.hip alone: conv._conv_backward asks and restates neither."""
+    csrc/conv_igemm.hip and csrc/conv_bf16.hip alone: conv._conv_backward and its two halves ask and restate neither."""
     import inspect
     from feature_intertwiner_amd import conv
-    src = inspect.getsource(conv._conv_backward)
+    src = "".join(inspect.getsource(f) for f in (conv._conv_backward, conv._weight_grad, conv._data_grad))
     for token in ("0x7fffff00", "% 16 == 0 and dz", "Cin == 64", "% 64", "(3, 3, (1, 1))"):
         assert token not in src, token
+
+
+def test_conv_owns_no_stream_of_its_own():
+    """Weight gradients run on the stream their layer's backward runs on: conv.py makes no stream and no event and waits
+    for none, and data_parallel has no weight-gradient stream to wait for."""
+    import inspect
+    from feature_intertwiner_amd import conv, data_parallel
+    src = inspect.getsource(conv)
+    for token in ("torch.cuda.Stream(", "wait_stream", "wait_event", "torch.cuda.Event"):
+        assert token not in src, token
+    assert not hasattr(data_parallel, "conv_wgrad_stream")
 
 
 def test_forward_kernel_selection_of_the_16bit_path_is_stated_once():

@@ -5,7 +5,7 @@ This is the path on which round 3 moved work between autograd nodes: the stem's 
 applied in a reader's data-gradient epilogue (conv.Gate), the shortcut / projection / FPN-lateral gradients handed over
 through GradBoxes and added (and masked) inside the first convolution's kernels, BatchNorm sums taken from the weight
 gradient, the top-down upsampling's one-pass backward.  Run with and without the per-step state of prepare_step
-(gradient arena, scaled W^T from the batched transpose, weight gradients on the second stream)."""
+(gradient arena, scaled W^T from the batched transpose, weight gradients queued and launched several at a time)."""
 import pytest
 import torch
 import torch.nn as nn
