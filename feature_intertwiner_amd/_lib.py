@@ -110,6 +110,7 @@ SIGNATURES = {
     "fi_conv2d_forward_live": (c_int, [c_void_p] * 7 + [c_int] * 16 + [c_void_p, c_void_p]),
     "fi_conv2d_forward_plan": (c_int, [c_void_p] * 7 + [c_int] * 16 + [_ip]),
     "fi_conv2d_weight_grad_plan": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 12 + [c_void_p, c_int, c_int, _ip, _ip]),
+    "fi_conv2d_weight_grad_split_plan": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 12 + [c_void_p, c_int, c_int, _ip, _ip]),
     "fi_conv2d_weight_grad_layout": (c_int, [c_void_p, c_void_p] + [c_int] * 11 + [_ip]),
     "fi_conv2d_weight_grad_plan_bf16": (c_int, [c_void_p] * 4 + [c_int] * 13 + [_ip, _ip]),
     "fi_conv2d_weight_grad_plan_f16": (c_int, [c_void_p] * 4 + [c_int] * 13 + [_ip, _ip]),

@@ -590,15 +590,26 @@ __global__ __launch_bounds__(kThreads, 4) void conv_fwd_kernel(const float *__re
 constexpr int PT_TH = 8, PT_TW = 16;        // 2-D tile: 8 stacked rows x 16 columns = 128 pixels
 constexpr int PT_PW = 24;                   // patch row: six 16-byte groups (2-D: columns X0-4 .. X0+19; flat: -4 .. 19)
 
+// Patch rows of a flat tile on a W-wide map: 128 consecutive pixels that start at column W - 1 touch
+// (W + 126) / W + 1 stacked rows, and the 3x3 window adds a halo row above and below.  13 for W = 14, 14 for W = 12
+// (a tile that starts at column 8 of a 12-wide row ends on column 3 eleven rows further down: 12 rows + halo).
+constexpr int patch_flat_rows(int W) { return (W + 126) / W + 3; }
+constexpr int PT_ROWS_FLAT = 13;            // the 14 x 14 RoI maps
+constexpr int PT_ROWS_FLAT_MAX = 14;        // 12-wide maps: their own instantiation of the kernel
+static_assert(patch_flat_rows(14) == PT_ROWS_FLAT && patch_flat_rows(12) == PT_ROWS_FLAT_MAX, "flat patch rows");
+static_assert(patch_flat_rows(10) > PT_ROWS_FLAT_MAX, "10-wide maps are not eligible");
+
 // FLAT = false: 2-D tiles (maps whose width is a multiple of 16).
-// FLAT = true : maps of 12..16 columns (14 x 14 RoI maps): a tile is 128 CONSECUTIVE pixels of the flattened
+// FLAT = true : maps of 12 or 14 columns (14 x 14 RoI maps): a tile is 128 CONSECUTIVE pixels of the flattened
 //               (stacked row, column) space -- no tile column is wasted on a 14-wide map; a lane's 4 pixels may
-//               then sit on two rows, so every pixel carries its own patch offsets.
-template <bool FLAT>
+//               then sit on two rows, so every pixel carries its own patch offsets.  FROWS: the patch rows a tile
+//               of the map's width can touch (patch_flat_rows).
+template <bool FLAT, int FROWS = PT_ROWS_FLAT>
 struct PatchShape {
-    static constexpr int ROWS = FLAT ? 13 : PT_TH + 2;         // patch rows (flat: up to 11 rows of 12+ pixels, + halo)
+    static constexpr int ROWS = FLAT ? FROWS : PT_TH + 2;      // patch rows (tile rows + halo)
     static constexpr int ZR = ROWS;                              // + one row of zeros
-    static constexpr int PP = FLAT ? 338 : 266;                  // floats per channel: (ROWS+1)*24 + 2 -> 8*PP = 16 (mod 32) banks
+    static constexpr int PP = (ROWS + 1) * PT_PW + 2;            // floats per channel: 266 / 338 / 362 -> 8*PP = 16 (mod 32) banks
+    static_assert((8 * PP) % 32 == 16, "patch pitch: the two channel halves of a wavefront on disjoint banks");
     // staged 16-byte groups per patch row.  Flat maps are at most 16 columns wide and a patch row starts at image
     // column -4: groups 0 and 5 (columns -4..-1 and 16..19) are outside every image -- zeroed once, never staged.
     static constexpr int GROUPS = FLAT ? 4 : PT_PW / 4;
@@ -715,12 +726,12 @@ __device__ __forceinline__ void patch_epilogue_pairs(const f32x16 (&acc)[4], con
     }
 }
 
-template <bool FLAT>
+template <bool FLAT, int FROWS = PT_ROWS_FLAT>
 __global__ __launch_bounds__(kThreads, 3) void conv3x3_patch_kernel(const float *__restrict__ x,
                                                                    const float *__restrict__ w, Epilogue ep,
                                                                    float *__restrict__ y, PatchGeom g)
 {
-    using SH = PatchShape<FLAT>;
+    using SH = PatchShape<FLAT, FROWS>;
     __shared__ __attribute__((aligned(16))) float Ps[2][BK][SH::PP];
 
     // XCD-aware order: XCD c owns a contiguous band of pixel tiles, Cout tiles innermost
@@ -1781,7 +1792,7 @@ __global__ __launch_bounds__(kThreads, 4) void conv_wgrad_vec_kernel(const float
 // conv3x3_patch_kernel: 3x3 / stride 1 / pad 1, same-size NCHW output, tap-major weights, 16-channel blocks,
 // 128-row Cout tiles, and at least 256 workgroups (one per CU: measured faster than the 64x64-tile kernel down
 // to there -- C4 of ResNet at batch 4 -- and slower below).
-// Returns 0 (not eligible), 1 (2-D tiles: width a multiple of 16) or 2 (flat tiles: even widths 12..16, e.g. the
+// Returns 0 (not eligible), 1 (2-D tiles: width a multiple of 16) or 2 (flat tiles: widths 12 and 14, e.g. the
 // 14 x 14 RoI maps; 8-byte aligned tensors).
 int patch_eligible(const ConvGeom &g, bool hwc, int weight_layout, const float *x, const float *y,
                    const float *residual)
@@ -1793,8 +1804,8 @@ int patch_eligible(const ConvGeom &g, bool hwc, int weight_layout, const float *
     const long mt = fi::ceil_div(g.Cout, 128);
     if (g.W % PT_TW == 0)
         return (long)fi::ceil_div(g.N * g.H, PT_TH) * (g.W / PT_TW) * mt >= 256 ? 1 : 0;
-    // flat tiles: 128 consecutive pixels touch at most (W + 126) / W rows, + 2 halo rows <= 13 patch rows
-    if (g.W < 16 && g.W % 2 == 0 && (g.W + 126) / g.W + 2 <= PatchShape<true>::ROWS && (uintptr_t)x % 8 == 0 &&
+    // flat tiles: the patch rows a tile of this width touches fit the kernel's largest instantiation
+    if (g.W < 16 && g.W % 2 == 0 && patch_flat_rows(g.W) <= PT_ROWS_FLAT_MAX && (uintptr_t)x % 8 == 0 &&
         (uintptr_t)y % 8 == 0 &&
         (residual == nullptr || (uintptr_t)residual % 8 == 0))
         return (long)fi::ceil_div(g.N * g.H * g.W, 128) * mt >= 512 ? 2 : 0;
@@ -2478,8 +2489,10 @@ int fi_conv2d_forward_live(const float *x, const float *weight, const float *bia
         pg.out_nhwc = g.out_nhwc;
         pg.zero = g.zero;
         const long blocks = (long)fi::ceil_div(pg.ptiles, 8) * 8 * pg.mtiles;
-        if (flat)
+        if (flat && patch_flat_rows(W) <= PT_ROWS_FLAT)
             hipLaunchKernelGGL(conv3x3_patch_kernel<true>, dim3((unsigned)blocks), dim3(kThreads), 0, st, x, weight, ep, y, pg);
+        else if (flat)
+            hipLaunchKernelGGL((conv3x3_patch_kernel<true, PT_ROWS_FLAT_MAX>), dim3((unsigned)blocks), dim3(kThreads), 0, st, x, weight, ep, y, pg);
         else
             hipLaunchKernelGGL(conv3x3_patch_kernel<false>, dim3((unsigned)blocks), dim3(kThreads), 0, st, x, weight, ep, y, pg);
         FI_HIP_CHECK(hipGetLastError());
@@ -2692,6 +2705,24 @@ int fi_conv2d_weight_grad_plan(const float *x, const float *dy, float *dweight, 
     const int nb = wgrad_batch_size(wgrad_batchable(g, x, dy, weight_layout), n, flags, true);
     *kernel_id = wgrad_conv_plan(g, nb).kernel_id;
     if (per_launch) *per_launch = nb;
+    return FI_OK;
+}
+
+int fi_conv2d_weight_grad_split_plan(const float *x, const float *dy, float *dweight, int N, int Cin, int H, int W,
+                                     int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
+                                     int weight_layout, float *dbias, int flags, int n, int *splits,
+                                     int *pixels_per_split)
+{
+    FI_REQUIRE(splits != nullptr && pixels_per_split != nullptr, "null pointer");
+    FI_REQUIRE(n >= 1, "empty batch / null pointer table");
+    ConvGeom g;
+    bool hwc;
+    const int rc = wgrad_checked(g, hwc, x, dy, dweight, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w,
+                                 weight_layout);
+    if (rc != FI_OK) return rc;
+    const WgradPlan plan = wgrad_conv_plan(g, wgrad_batch_size(wgrad_batchable(g, x, dy, weight_layout), n, flags, true));
+    *splits = plan.splits;
+    *pixels_per_split = plan.pps;
     return FI_OK;
 }
 

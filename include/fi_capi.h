@@ -419,6 +419,12 @@ int fi_conv2d_weight_grad(const float *x, const float *dy, float *dweight, int N
 int fi_conv2d_weight_grad_plan(const float *x, const float *dy, float *dweight, int N, int Cin, int H, int W, int Cout,
                                int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int weight_layout,
                                float *dbias, int flags, int n, int *kernel_id, int *per_launch);
+/* How that launch cuts the N * OH * OW pixels it sums over (same arguments, same checks, host-only): *splits pixel splits of
+ * *pixels_per_split pixels each, the last one shorter where splits * pixels_per_split exceeds the pixel count. */
+int fi_conv2d_weight_grad_split_plan(const float *x, const float *dy, float *dweight, int N, int Cin, int H, int W,
+                                     int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
+                                     int weight_layout, float *dbias, int flags, int n, int *splits,
+                                     int *pixels_per_split);
 /* Which dW layout fi_conv2d_weight_grad accepts for this geometry and these pointers (host-only, like the plan queries):
  * *weight_layout = 1 where a tap-major request ([Cout][R][S][Cin]) passes its checks, else 0. */
 int fi_conv2d_weight_grad_layout(const float *x, const float *dy, int N, int Cin, int H, int W, int Cout, int R, int S,

@@ -149,6 +149,13 @@ def test_plan_queries_name_the_kernel_on_both_sides_of_every_threshold():
     assert fwd(1, 16, 120, 128, 256, 3, 1, 1, 1) == "conv_fwd_bm64_3x3"                 # 240
     assert fwd(168, 16, 14, 14, 256, 3, 1, 1, 1) == "conv3x3_patch_flat"                # 516
     assert fwd(166, 16, 14, 14, 256, 3, 1, 1, 1) == "conv_fwd_bm64_3x3"                 # 510
+    # 12-wide maps: flat tiles too (their 14 patch rows are an instantiation of their own), forward and data gradient; a
+    # 10-wide tile would touch 16
+    assert fwd(227, 16, 12, 12, 256, 3, 1, 1, 1) == "conv3x3_patch_flat"                # 512
+    assert fwd(227, 16, 12, 12, 256, 3, 1, 1, 2) == "conv3x3_patch_flat"
+    assert fwd(273, 16, 10, 12, 256, 3, 1, 1, 1) == "conv3x3_patch_flat"                # 512, H != W
+    assert fwd(226, 16, 12, 12, 256, 3, 1, 1, 1) == "conv_fwd_bm64_3x3"                 # 510
+    assert fwd(400, 16, 10, 10, 256, 3, 1, 1, 1) == "conv_fwd_bm128_3x3"                # width 10
     assert fwd(168, 16, 14, 14, 256, 3, 1, 1, 1, gate=G + 8) == "conv3x3_patch_flat"
     # a gate that is 4- but not 8-byte aligned: not the flat kernel -- the generic one, whose 516 tiles take 128 rows
     assert fwd(168, 16, 14, 14, 256, 3, 1, 1, 1, gate=G + 4) == "conv_fwd_bm128_3x3"
@@ -180,6 +187,16 @@ def test_plan_queries_name_the_kernel_on_both_sides_of_every_threshold():
 
     assert per_launch(1, 6) == 6 and per_launch(1, 6, flags=0) == 1 and per_launch(1, 6, x=X + 4) == 1
     assert per_launch(6, 1) == 1 and per_launch(1, 26) == _lib.WGRAD_BATCH_MAX
+
+    # ... and how the launch cuts its pixels: (splits, pixels per split), a multiple of 16, the last split the short one
+    def splits(N, Cin, H, W, Cout, k, pad, n=1):
+        return _lib.wgrad_plan(L.fi_conv2d_weight_grad_split_plan, X, Y, Wt, N, Cin, H, W, Cout, k, k, 1, 1, pad, pad, 1, None,
+                               _lib.OUTPUTS_ZEROED, n)
+
+    assert splits(6, 1024, 64, 64, 256, 1, 0) == (48, 512) and splits(5, 1024, 64, 64, 256, 1, 0) == (32, 640)
+    assert splits(3, 128, 18, 22, 128, 3, 1) == (3, 400)                                # 1188 pixels: the last split has 388
+    assert splits(1, 128, 4, 4, 128, 3, 1) == (1, 16)
+    assert L.fi_conv2d_weight_grad_split_plan(X, Y, Wt, 1, 128, 4, 4, 128, 3, 3, 1, 1, 1, 1, 1, None, 0, 1, None, None) == -1
 
     # fi_conv2d_weight_grad_layout: tap-major dW for whole 128-channel tiles, or 64 channels on a same-size stride-1 layer
     # with aligned operands; a tap-major request is rejected on exactly the shapes that answer 0
