@@ -23,6 +23,10 @@ EVAL_HEADERS = [os.path.join("..", "..", "include", "fi_eval.h")]
 COCOEVAL_LIB_PATH = os.path.join(_HERE, "libfi_cocoeval.so")
 COCOEVAL_SOURCES = ["cocoeval.hip"]
 COCOEVAL_HEADERS = [os.path.join("..", "..", "include", "fi_cocoeval.h")]
+# COCO polygon ground truth -> RLE (include/fi_cocomask.h): a fourth library, built the same way
+COCOMASK_LIB_PATH = os.path.join(_HERE, "libfi_cocomask.so")
+COCOMASK_SOURCES = ["cocomask.hip"]
+COCOMASK_HEADERS = [os.path.join("..", "..", "include", "fi_cocomask.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
@@ -61,7 +65,7 @@ def _compile(sources, headers, force, verbose):
 
 
 def build_hip(force=False, verbose=False):
-    """Builds libfi_hip.so, libfi_eval.so and libfi_cocoeval.so; returns the path of the first."""
+    """Builds libfi_hip.so, libfi_eval.so, libfi_cocoeval.so and libfi_cocomask.so; returns the path of the first."""
     objs = _compile(SOURCES, HEADERS, force, verbose)
     if force or _stale(LIB_PATH, objs):
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
@@ -69,7 +73,8 @@ def build_hip(force=False, verbose=False):
             print(" ".join(cmd))
         subprocess.check_call(cmd)
     for lib, sources, headers in ((EVAL_LIB_PATH, EVAL_SOURCES, EVAL_HEADERS),
-                                  (COCOEVAL_LIB_PATH, COCOEVAL_SOURCES, COCOEVAL_HEADERS)):
+                                  (COCOEVAL_LIB_PATH, COCOEVAL_SOURCES, COCOEVAL_HEADERS),
+                                  (COCOMASK_LIB_PATH, COCOMASK_SOURCES, COCOMASK_HEADERS)):
         objs = _compile(sources, HEADERS + headers, force, verbose)
         if force or _stale(lib, objs + [LIB_PATH]):
             cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + [

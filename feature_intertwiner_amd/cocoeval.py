@@ -82,7 +82,8 @@ def rle_from_string(s):
 def _segm_counts(segm, what):
     if not isinstance(segm, dict) or "counts" not in segm or "size" not in segm:
         raise FiError("%s: 'segmentation' must be an uncompressed RLE {'size', 'counts'} or a COCO RLE string; "
-                      "polygons (rleFrPoly) are not supported" % what)
+                      "polygons are converted only by pack_ground_truth(..., image_sizes=...) / load_ground_truth "
+                      "(cocomask.ann_to_rle)" % what)
     c = segm["counts"]
     c = rle_from_string(c) if isinstance(c, (bytes, str)) else np.asarray(c, np.int64).astype(np.uint32)
     h, w = (int(v) for v in segm["size"])
@@ -135,14 +136,17 @@ def _pack(L, dev, image_id, category_id, box, area, ann_id, crowd, score, rle_li
     P.box = _up(np.asarray(box, np.float64).reshape(n, 4), torch.float64, dev)
     P.area = _up(np.asarray(area, np.float64).reshape(n), torch.float64, dev)
     if rle_list is not None:
-        lens = np.array([c.size for c, _, _ in rle_list], np.int64)
-        desc = np.zeros((n, 4), np.int64)
-        desc[:, 0] = np.cumsum(lens) - lens
-        desc[:, 1] = lens
-        desc[:, 2:] = np.array([(h, w) for _, h, w in rle_list], np.int64).reshape(n, 2)
-        flat = np.concatenate([c for c, _, _ in rle_list] + [np.zeros(1, np.uint32)])
-        P.rles = _up(desc, torch.int64, dev)
-        P.counts = _up(flat.view(np.int32), torch.int32, dev)
+        if isinstance(rle_list, tuple):                       # already on the device: cocomask.ann_to_rle
+            P.rles, P.counts = rle_list
+        else:
+            lens = np.array([c.size for c, _, _ in rle_list], np.int64)
+            desc = np.zeros((n, 4), np.int64)
+            desc[:, 0] = np.cumsum(lens) - lens
+            desc[:, 1] = lens
+            desc[:, 2:] = np.array([(h, w) for _, h, w in rle_list], np.int64).reshape(n, 2)
+            flat = np.concatenate([c for c, _, _ in rle_list] + [np.zeros(1, np.uint32)])
+            P.rles = _up(desc, torch.int64, dev)
+            P.counts = _up(flat.view(np.int32), torch.int32, dev)
         P.rle_box = torch.empty(n, 4, dtype=torch.float64, device=dev)
         P.rle_area = torch.empty(n, dtype=torch.float64, device=dev)
         with torch.cuda.device(dev):
@@ -156,10 +160,12 @@ def _pack(L, dev, image_id, category_id, box, area, ann_id, crowd, score, rle_li
     return P
 
 
-def pack_ground_truth(annotations, image_ids, category_ids, device=None):
+def pack_ground_truth(annotations, image_ids, category_ids, device=None, image_sizes=None):
     """The ground truth of COCOeval: a list of COCO annotation dicts ('id', 'image_id', 'category_id', 'bbox',
-    'area', 'iscrowd' and, for segm, 'segmentation' as an uncompressed RLE or a COCO string) and the image and
-    category ids of the data set (COCO.getImgIds() / getCatIds()).  Returns a device-resident, reusable object."""
+    'area', 'iscrowd' and, for segm, 'segmentation' as a polygon list, an uncompressed RLE or a COCO string) and the
+    image and category ids of the data set (COCO.getImgIds() / getCatIds()).  Polygons need `image_sizes`, a dict
+    image id -> (height, width); they are converted on the GPU as COCO.annToRLE does (cocomask.ann_to_rle).
+    Returns a device-resident, reusable object."""
     L = load()
     dev = _device(device)
     anns = list(annotations)
@@ -169,13 +175,38 @@ def pack_ground_truth(annotations, image_ids, category_ids, device=None):
     seg = [("segmentation" in a) for a in anns]
     if any(seg) and not all(seg):
         raise FiError("pack_ground_truth: some annotations have a 'segmentation' and some have none")
-    rl = [_segm_counts(a["segmentation"], "pack_ground_truth") for a in anns] if anns and all(seg) else None
+    rl = None
+    if anns and all(seg):
+        if any(isinstance(a["segmentation"], (list, tuple)) for a in anns):
+            if image_sizes is None:
+                raise FiError("pack_ground_truth: polygons in 'segmentation' need image_sizes = {image id: (height, "
+                              "width)} (or load_ground_truth on the whole data set)")
+            from . import cocomask
+            rl = cocomask.ann_to_rle(anns, image_sizes, dev)
+        else:
+            rl = [_segm_counts(a["segmentation"], "pack_ground_truth") for a in anns]
     P = _pack(L, dev, [a["image_id"] for a in anns], [a["category_id"] for a in anns],
               [a["bbox"] for a in anns], [a["area"] for a in anns], ids,
               [1 if a.get("iscrowd") else 0 for a in anns], np.zeros(len(anns)), rl, False, None)
     P.image_ids = np.unique(np.asarray(list(image_ids), np.int64))
     P.category_ids = np.unique(np.asarray(list(category_ids), np.int64))
     return P
+
+
+def load_ground_truth(source, device=None):
+    """pack_ground_truth of a whole COCO data set: `source` is the path of an instances_*.json or the loaded dict.
+    Image sizes come from 'images'; image and category ids are those of COCO.getImgIds() / getCatIds()."""
+    if isinstance(source, dict):
+        data = source
+    else:
+        import json
+        with open(source) as f:
+            data = json.load(f)
+    for key in ("images", "categories", "annotations"):
+        if key not in data:
+            raise FiError("load_ground_truth: the data set has no %r" % key)
+    sizes = {im["id"]: (im["height"], im["width"]) for im in data["images"]}
+    return pack_ground_truth(data["annotations"], list(sizes), [c["id"] for c in data["categories"]], device, sizes)
 
 
 def pack_results(results, device=None):

@@ -327,7 +327,8 @@ def test_step(model, molded_images, image_metas, image_shapes=None, windows=None
 def evaluate_coco(results, ground_truth, iou_type="bbox", img_ids=None):
     """The end of test_model (lib/workflow.py:458-465): loadRes, COCOeval(coco_api, coco_results, iou_type) with
     params.imgIds = img_ids, evaluate(), accumulate(), summarize().  `results` are the dicts of test_step,
-    `ground_truth` a cocoeval.pack_ground_truth object.  Returns (mAP, evaluation) with mAP = stats[0]."""
+    `ground_truth` a cocoeval.load_ground_truth / pack_ground_truth object (polygon segmentations are converted there,
+    as COCO.annToRLE does).  Returns (mAP, evaluation) with mAP = stats[0]."""
     from . import cocoeval
     evaluation = cocoeval.evaluate(ground_truth, cocoeval.pack_results(results, ground_truth.device), iou_type,
                                    img_ids)
