@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libfi_hip.so")
 SOURCES = ["fi_core.hip", "crop_and_resize.hip", "roi_pool.hip", "nms.hip", "sinkhorn.hip",
-           "class_mean.hip", "conv_igemm.hip", "conv1x1_ring.hip", "conv_bf16.hip", "conv_f16.hip", "sgd.hip", "glue.hip", "proposal.hip", "targets.hip", "losses.hip", "dev_stage.hip", "meta_stats.hip"]
+           "class_mean.hip", "conv_igemm.hip", "conv1x1_ring.hip", "conv3x3_wino.hip", "conv_bf16.hip", "conv_f16.hip", "sgd.hip", "glue.hip", "proposal.hip", "targets.hip", "losses.hip", "dev_stage.hip", "meta_stats.hip"]
 HEADERS = ["fi_common.h", os.path.join("..", "..", "include", "fi_capi.h")]
 # the evaluation path (inference post-processing, include/fi_eval.h): its own library, linked against libfi_hip.so
 EVAL_LIB_PATH = os.path.join(_HERE, "libfi_eval.so")

@@ -2046,6 +2046,7 @@ struct FwdPlan {
     FwdPath path;
     bool bm64;        // FWD_GENERIC: 64-row tiles (128 otherwise)
     bool hwc;         // tap-major weights: the fast gather path
+    bool wino;        // FWD_PATCH_FLAT: the Winograd F(2x2,3x3) form (conv3x3_wino_flat_kernel); same counter
     int kernel_id;    // FI_K_*: the profiling counter of the launch
 };
 
@@ -2071,6 +2072,7 @@ int plan_forward(ConvGeom &g, FwdPlan &p, const float *x, const float *weight, c
     p.hwc = (Cin % BK == 0) && (R * S <= 64) && (weight_layout >= 1 || R * S == 1);
     FI_REQUIRE(p.hwc || weight_layout == 0, "weight_layout 1/2/3 needs Cin % 16 == 0 and R*S <= 64");
     g.flip = (weight_layout == 2) ? 1 : 0;
+    p.wino = false;
     // generic kernel: 64-row tiles for narrow layers, and for grids that would leave the chip under-filled with
     // 128-row tiles (fewer than 2 workgroups per CU): C4/C5 of the backbone at batch 4
     p.bm64 = Cout <= 64 || (long)fi::ceil_div(g.P, BN) * fi::ceil_div(Cout, 128) < 512;
@@ -2097,6 +2099,9 @@ int plan_forward(ConvGeom &g, FwdPlan &p, const float *x, const float *weight, c
     if (patch) {
         p.path = patch == 2 ? FWD_PATCH_FLAT : FWD_PATCH;
         p.kernel_id = FI_K_CONV3X3_PATCH + (patch - 1);
+        // 14 x 14 maps (7 x 7 Winograd tiles, none ragged) with at least 4 channel blocks: 2.25x fewer MFMAs.  The
+        // launch fills the chip by the flat kernel's own rule (patch == 2); FI_NO_WINOGRAD keeps the direct form.
+        p.wino = patch == 2 && H == fi::WINO_HW && W == fi::WINO_HW && Cin % BK == 0 && Cin >= 64 && !getenv("FI_NO_WINOGRAD");
     } else if (reg1x1) {
         p.path = FWD_REG1X1;
         p.kernel_id = FI_K_CONV1X1_REG;
@@ -2473,6 +2478,12 @@ int fi_conv2d_forward_live(const float *x, const float *weight, const float *bia
         cg.zero = g.zero;
         const long blocks = (long)fi::ceil_div(cg.ptiles, 8) * 8 * cg.mtiles;
         hipLaunchKernelGGL(conv1x1_reg_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, x, weight, ep, y, cg);
+        FI_HIP_CHECK(hipGetLastError());
+        return FI_OK;
+    }
+    if (plan.path == FWD_PATCH_FLAT && plan.wino) {
+        const fi::WinoArgs wa = {x, weight, bias, scale, residual, gate, y, g.zero, N, Cin, Cout, relu, g.flip};
+        fi::launch_conv3x3_wino_flat(wa, st);
         FI_HIP_CHECK(hipGetLastError());
         return FI_OK;
     }

@@ -29,6 +29,16 @@ struct RingArgs {
 };
 int launch_conv1x1_ring(const RingArgs &a, hipStream_t st);
 
+// conv3x3_wino.hip (launched by fi_conv2d_forward_live when plan_forward picks the Winograd form of the flat patch slot)
+constexpr int WINO_HW = 14;          // the map size the kernel is written for (7 x 7 tiles of 2 x 2 pixels)
+struct WinoArgs {
+    const float *x, *w, *bias, *scale, *residual, *gate;
+    float *y;
+    const float *zero;
+    int N, Cin, Cout, relu, flip;
+};
+void launch_conv3x3_wino_flat(const WinoArgs &a, hipStream_t st);
+
 #define FI_HIP_CHECK(expr)                                                         \
     do {                                                                           \
         hipError_t _e = (expr);                                                    \

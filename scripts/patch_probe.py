@@ -12,7 +12,7 @@ def run(name, N, Cin, H, W, Cout, key, iters=20):
     torch.cuda.synchronize(); _lib.prof_reset(); _lib.prof_enable(True)
     for _ in range(iters): _conv_fwd(x, w, b, (1, 1), (1, 1), relu=True, scale=sc)
     torch.cuda.synchronize(); _lib.prof_enable(False)
-    n, ms = _lib.prof_get(key); us = ms / max(n, 1) * 1e3; fl = 2.0 * N * H * W * Cin * Cout * 9
+    n, ms = _lib.prof_get(key); us = ms / max(n, 1) * 1e3 or float("nan"); fl = 2.0 * N * H * W * Cin * Cout * 9
     print(json.dumps({"layer": name, "us": round(us, 1), "TFLOPs": round(fl / us / 1e6, 1), "n": n,
                       "tiles": ((N * H * W + 127) // 128) * ((Cout + 127) // 128)}))
 run("C4 3x3 256 N4 (256 tiles)", 4, 256, 64, 64, 256, "conv3x3_patch")
@@ -23,3 +23,35 @@ run("C5 3x3 512 N4 (128 tiles)", 4, 512, 32, 32, 512, "conv3x3_patch")
 run("C3 3x3 128 N4 (512 tiles)", 4, 128, 128, 128, 128, "conv3x3_patch")
 run("FPN P2 3x3 256", 4, 256, 256, 256, 256, "conv3x3_patch")
 run("mask 14x14 256 N1376", 1376, 256, 14, 14, 256, "conv3x3_patch_flat")
+run("mask 14x14 256 N672", 672, 256, 14, 14, 256, "conv3x3_patch_flat")
+
+
+def run_flat(name, N, Cin, Cout=256, rounds=5, iters=8):
+    """The flat slot with its Winograd form and with FI_NO_WINOGRAD=1 (the library reads the switch per call), rounds of
+    the two interleaved in this process on the same random data: median and min us per variant, TFLOP/s in direct-form
+    flops (the Winograd form issues 16/36 of the MFMAs, so its figure may read above the MFMA peak)."""
+    x = torch.randn(N, Cin, 14, 14, device=DEV)
+    w = (torch.randn(Cout, Cin, 3, 3, device=DEV) * 0.05).contiguous(memory_format=torch.channels_last)
+    sc = torch.rand(Cout, device=DEV) + 0.5; b = torch.randn(Cout, device=DEV)
+    key = "conv3x3_patch_flat"; us = {"winograd": [], "direct": []}
+    for r in range(rounds + 1):
+        for variant in ("winograd", "direct"):
+            if variant == "direct": os.environ["FI_NO_WINOGRAD"] = "1"
+            else: os.environ.pop("FI_NO_WINOGRAD", None)
+            torch.cuda.synchronize(); _lib.prof_reset(); _lib.prof_enable(True)
+            for _ in range(iters): _conv_fwd(x, w, b, (1, 1), (1, 1), relu=True, scale=sc)
+            torch.cuda.synchronize(); _lib.prof_enable(False)
+            n, ms = _lib.prof_get(key); assert n == iters, (n, iters)
+            if r: us[variant].append(ms / n * 1e3)                 # round 0 warms up
+    os.environ.pop("FI_NO_WINOGRAD", None)
+    fl = 2.0 * N * 196 * Cin * Cout * 9; out = {"layer": name}
+    for variant, v in us.items():
+        v.sort(); med = v[len(v) // 2]
+        out[variant] = {"us_median": round(med, 1), "us_min": round(v[0], 1), "TFLOPs_direct_form": round(fl / med / 1e6, 1)}
+    out["speedup_median"] = round(out["direct"]["us_median"] / out["winograd"]["us_median"], 3)
+    print(json.dumps(out))
+
+
+for n_img in (1376, 672):
+    for cin in (256, 128, 64):
+        run_flat("mask 14x14 %d->256 N%d" % (cin, n_img), n_img, cin)
