@@ -8,20 +8,90 @@ runs 2L+6 small kernels per Sinkhorn problem (lib/OT_module.py:95-135); here all
 3*bs problems of a forward go through ONE launch of the HIP Sinkhorn kernel
 (feature_intertwiner_amd/csrc/sinkhorn.hip).
 
-Autograd: with `no_bp_P_L=True` (the reference default and the only setting the model
-uses) the transport plan P is a constant (:129-131), so d loss / d C = P and the
-backward is two small batched products with the saved plan.  The row normalisation
+Autograd: with `no_bp_P_L=True` (the reference default, and the model's unless
+DEV.OT_NO_BP_P_L says otherwise) the transport plan P is a constant (:129-131), so
+d loss / d C = P and the backward is two small batched products with the saved plan.
+With `no_bp_P_L=False` the loss is differentiated through the L iterations: ONE launch of
+csrc/sinkhorn_bp.hip (libfi_ot.so, include/fi_ot.h) returns the same loss bits and
+d loss / d C, which takes the plan's place in the same backward.  The row normalisation
 `x / (||x|| + 1e-20)` is done out of place in torch (the reference's in-place `x /= ...`
 on the critic's ReLU output, :111-112, raises in modern autograd; forward values are
 identical).
 """
+import ctypes
+import os
+
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .conv import Conv1d, Conv2d
 
 EPS = 1e-20
+
+OT_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfi_ot.so")
+_p, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+# name -> (restype, argtypes); mirrors include/fi_ot.h one to one
+OT_SIGNATURES = {
+    "fi_ot_sinkhorn_backprop_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "fi_ot_sinkhorn_backprop": (_i, [_p, _p, _i, _i, _i, _f, _i, _i, _p, _p, _p, ctypes.c_size_t, _p]),
+}
+_ot = None
+
+
+def load_ot():
+    """Load libfi_ot.so (after libfi_hip.so, which it links against) and attach the signatures."""
+    global _ot
+    if _ot is not None:
+        return _ot
+    _lib.load()
+    if not os.path.exists(OT_LIB_PATH):
+        raise _lib.FiError("libfi_ot.so not found at %s -- build it with `python -m feature_intertwiner_amd.build` "
+                           "(there is no CPU/PyTorch fallback)" % OT_LIB_PATH)
+    L = ctypes.CDLL(OT_LIB_PATH)
+    for name, (res, args) in OT_SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype = res
+        fn.argtypes = args
+    _ot = L
+    return L
+
+
+def _cost_backward(cost_mode, x, y, plan, grad_loss, difference_form=False):
+    """(gx, gy) of sum_p grad_loss[p] <plan_p, C_p(x, y)> with `plan` a constant: the transport plan in the detached
+    form, d loss / d C (entries of either sign) in the differentiable one.
+    difference_form (l2 cost): sum_j w_ij (x_i - y_j) from the differences themselves, one feature column at a time,
+    not as x_i sum_j w_ij - sum_j w_ij y_j: with w = plan / |x_i - y_j| the two sums are large where a pair is close and
+    cancel (at D = 1, S = 256 the result is off by 1.7e-4 of its largest element; the difference form by 1e-6)."""
+    g = grad_loss.view(-1, 1, 1)
+    if cost_mode == 1 and difference_form:
+        dist = torch.cdist(x, y, compute_mode="donot_use_mm_for_euclid_dist")
+        w = torch.where(dist > 0, plan / dist.clamp_min(1e-30), torch.zeros_like(plan))
+        gx, gy = torch.empty_like(x), torch.empty_like(y)
+        for d in range(x.size(2)):
+            wd = w * (x[:, :, d, None] - y[:, None, :, d])
+            gx[:, :, d] = wd.sum(2)
+            gy[:, :, d] = -wd.sum(1)
+        return gx * g, gy * g
+    if cost_mode == 2 and x.size(2) == 1:
+        # D = 1 (the model's 1-D form): the two plan-vector products as broadcast multiply + row / column sums
+        gx = -(plan * y.transpose(1, 2)).sum(2, keepdim=True) * g
+        gy = -(plan * x).sum(1).unsqueeze(2) * g
+    elif cost_mode == 2:
+        gx = -torch.bmm(plan, y) * g
+        gy = -torch.bmm(plan.transpose(1, 2), x) * g
+    else:
+        # d|x_i - y_j| / dx_i = (x_i - y_j) / |x_i - y_j|, and 0 at coincident points (the subgradient
+        # torch.norm's backward uses); dividing by a clamped distance instead would weight the
+        # (x_i - y_j) = 0 pairs -- every pair of ReLU-dead critic outputs -- by P / 1e-30.  The distances come
+        # from the differences, as the kernel computes its cost: cdist's default for more than 25 samples is
+        # |x|^2 + |y|^2 - 2 <x, y>, whose cancellation leaves a pair 1e-3 apart with a distance off by tens of percent
+        dist = torch.cdist(x, y, compute_mode="donot_use_mm_for_euclid_dist")
+        w = torch.where(dist > 0, plan / dist.clamp_min(1e-30), torch.zeros_like(plan))
+        gx = (w.sum(2, keepdim=True) * x - torch.bmm(w, y)) * g
+        gy = (w.sum(1).unsqueeze(2) * y - torch.bmm(w.transpose(1, 2), x)) * g
+    return gx, gy
 
 
 class _SinkhornLoss(torch.autograd.Function):
@@ -50,39 +120,64 @@ class _SinkhornLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_loss):
         x, y, plan = ctx.saved_tensors
-        g = grad_loss.view(-1, 1, 1)
-        if ctx.cost_mode == 2 and x.size(2) == 1:
-            # D = 1 (the model's 1-D form): the two plan-vector products as broadcast multiply + row / column sums
-            gx = -(plan * y.transpose(1, 2)).sum(2, keepdim=True) * g
-            gy = -(plan * x).sum(1).unsqueeze(2) * g
-        elif ctx.cost_mode == 2:
-            gx = -torch.bmm(plan, y) * g
-            gy = -torch.bmm(plan.transpose(1, 2), x) * g
-        else:
-            # d|x_i - y_j| / dx_i = (x_i - y_j) / |x_i - y_j|, and 0 at coincident points (the subgradient
-            # torch.norm's backward uses); dividing by a clamped distance instead would weight the
-            # (x_i - y_j) = 0 pairs -- every pair of ReLU-dead critic outputs -- by P / 1e-30.  The distances come
-            # from the differences, as the kernel computes its cost: cdist's default for more than 25 samples is
-            # |x|^2 + |y|^2 - 2 <x, y>, whose cancellation leaves a pair 1e-3 apart with a distance off by tens of percent
-            dist = torch.cdist(x, y, compute_mode="donot_use_mm_for_euclid_dist")
-            w = torch.where(dist > 0, plan / dist.clamp_min(1e-30), torch.zeros_like(plan))
-            gx = (w.sum(2, keepdim=True) * x - torch.bmm(w, y)) * g
-            gy = (w.sum(1).unsqueeze(2) * y - torch.bmm(w.transpose(1, 2), x)) * g
+        gx, gy = _cost_backward(ctx.cost_mode, x, y, plan, grad_loss)
         return gx, gy, None, None, None
 
 
-def sinkhorn_loss(x, y, epsilon_inv=1.0, L=5, C_form="cosine"):
-    """Batched `_sinkhorn_iterate` (lib/OT_module.py:104-135): x, y [P, S, D] -> loss [P]."""
+class _SinkhornLossBackprop(torch.autograd.Function):
+    """loss[p] = <P_p, C_p> differentiated through the L iterations (P not detached): fi_ot_sinkhorn_backprop returns the
+    loss (the bits of fi_sinkhorn_forward's) and d loss / d C in one launch; the chain from C to x, y is
+    _cost_backward's.  Used only when a gradient is needed.  First derivatives only."""
+
+    @staticmethod
+    def forward(ctx, x, y, eps_inv, L, cost_mode):
+        _lib.require_cuda(x, y)
+        lib = load_ot()
+        x = x.contiguous().float()
+        y = y.contiguous().float()
+        P, S, D = x.shape
+        # loss, d loss / d C and the workspace from the caching allocator, on the current stream
+        loss = torch.empty((P,), device=x.device, dtype=torch.float32)
+        dcost = torch.empty((P, S, S), device=x.device, dtype=torch.float32)
+        nbytes = lib.fi_ot_sinkhorn_backprop_workspace_bytes(P, S, int(L))
+        ws = torch.empty((max(1, nbytes // 4),), device=x.device, dtype=torch.float32)
+        with torch.cuda.device(x.device):
+            _lib.check(lib.fi_ot_sinkhorn_backprop(_lib.ptr(x), _lib.ptr(y), P, S, D, float(eps_inv), int(L),
+                                                   int(cost_mode), _lib.ptr(loss), _lib.ptr(dcost), _lib.ptr(ws),
+                                                   ws.numel() * 4, _lib.current_stream()), "fi_ot_sinkhorn_backprop")
+        ctx.cost_mode = int(cost_mode)
+        ctx.save_for_backward(x, y, dcost)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        x, y, dcost = ctx.saved_tensors
+        gx, gy = _cost_backward(ctx.cost_mode, x, y, dcost, grad_loss, difference_form=True)
+        return gx, gy, None, None, None
+
+
+def _sinkhorn_apply(x, y, epsilon_inv, L, cost_mode, detach_plan):
+    if not detach_plan and torch.is_grad_enabled() and (x.requires_grad or y.requires_grad):
+        return _SinkhornLossBackprop.apply(x, y, epsilon_inv, L, cost_mode)
+    return _SinkhornLoss.apply(x, y, epsilon_inv, L, cost_mode)      # no gradient asked for: the forward alone
+
+
+def sinkhorn_loss(x, y, epsilon_inv=1.0, L=5, C_form="cosine", detach_plan=True):
+    """Batched `_sinkhorn_iterate` (lib/OT_module.py:104-135): x, y [P, S, D] -> loss [P].  detach_plan is the
+    reference's no_bp_P_L: True (default) treats the plan as a constant in the backward, False differentiates through
+    the L iterations (same loss bits; S <= 256; first derivatives only)."""
     if C_form == "cosine":
         xn = x / (torch.norm(x, p=2, dim=2, keepdim=True) + EPS)
         yn = y / (torch.norm(y, p=2, dim=2, keepdim=True) + EPS)
-        loss = _SinkhornLoss.apply(xn, yn, epsilon_inv, L, 2)
+        loss = _sinkhorn_apply(xn, yn, epsilon_inv, L, 2, detach_plan)
     elif C_form == "l2":
-        loss = _SinkhornLoss.apply(x, y, epsilon_inv, L, 1)
+        loss = _sinkhorn_apply(x, y, epsilon_inv, L, 1, detach_plan)
     else:
         raise ValueError("unknown C_form %r" % (C_form,))
     if _lib.TAP is not None:
-        _lib.TAP("sinkhorn", x=x, y=y, eps_inv=float(epsilon_inv), L=int(L), C_form=C_form, loss=loss)
+        _lib.TAP("sinkhorn", x=x, y=y, eps_inv=float(epsilon_inv), L=int(L), C_form=C_form, loss=loss,
+                 detach_plan=bool(detach_plan))
     return loss
 
 
@@ -114,13 +209,9 @@ class OptTrans(nn.Module):
     def __init__(self, config, ch_x, spatial_x=-1, ch_y=-1, spatial_y=-1,
                  epsilon=1., L=5, remove_bias=False, C_form='cosine', no_bp_P_L=True, skip_critic=False):
         super(OptTrans, self).__init__()
-        if not no_bp_P_L:
-            raise NotImplementedError(
-                "OptTrans(no_bp_P_L=False) back-propagates through the Sinkhorn iterations; the HIP "
-                "kernel implements the detached-plan form the model uses (reference default)")
         self.config = config
         self.epsilon = 1. / epsilon   # stored inverted, as the reference (:13)
-        self.L, self.remove_bias, self.no_bp_P_L = L, remove_bias, no_bp_P_L
+        self.L, self.remove_bias, self.no_bp_P_L = L, remove_bias, bool(no_bp_P_L)
         self.C_form, self.skip_critic = C_form, skip_critic
         self.two_dim = spatial_x > 1
         ch_y = ch_x if ch_y == -1 else ch_y
@@ -137,11 +228,11 @@ class OptTrans(nn.Module):
         cx = self._critic_samples(x_upsample)   # [bs, S, D]
         cy = self._critic_samples(y)
         if self.remove_bias:
-            return sinkhorn_loss(cx, cy, self.epsilon, self.L, self.C_form)
+            return sinkhorn_loss(cx, cy, self.epsilon, self.L, self.C_form, self.no_bp_P_L)
         # the three terms 2*T(x_up, y) - T(x_up, x_up) - T(y, y) as 3*bs problems, one launch
         xs = torch.cat((cx, cx, cy), 0)
         ys = torch.cat((cy, cx, cy), 0)
-        t = sinkhorn_loss(xs, ys, self.epsilon, self.L, self.C_form)
+        t = sinkhorn_loss(xs, ys, self.epsilon, self.L, self.C_form, self.no_bp_P_L)
         return 2 * t[:bs] - t[bs:2 * bs] - t[2 * bs:]
 
     def _critic_samples(self, v):
@@ -151,4 +242,4 @@ class OptTrans(nn.Module):
     def _basic_compute_loss(self, x, y):
         """T(x, y) of the reference (:83-102): critic on both, one Sinkhorn per sample."""
         return sinkhorn_loss(self._critic_samples(x), self._critic_samples(y), self.epsilon, self.L,
-                             self.C_form)
+                             self.C_form, self.no_bp_P_L)

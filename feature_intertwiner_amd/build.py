@@ -15,6 +15,8 @@ LIB_PATH = os.path.join(_HERE, "libfi_hip.so")
 SOURCES = ["fi_core.hip", "crop_and_resize.hip", "roi_pool.hip", "nms.hip", "sinkhorn.hip",
            "class_mean.hip", "conv_igemm.hip", "conv1x1_ring.hip", "conv3x3_wino.hip", "conv_bf16.hip", "conv_f16.hip", "sgd.hip", "glue.hip", "proposal.hip", "targets.hip", "losses.hip", "dev_stage.hip", "meta_stats.hip"]
 HEADERS = ["fi_common.h", os.path.join("..", "..", "include", "fi_capi.h")]
+# device code that sinkhorn.hip (libfi_hip.so) and sinkhorn_bp.hip (libfi_ot.so) share
+SINKHORN_HEADERS = ["sinkhorn_dev.h"]
 # the evaluation path (inference post-processing, include/fi_eval.h): its own library, linked against libfi_hip.so
 EVAL_LIB_PATH = os.path.join(_HERE, "libfi_eval.so")
 EVAL_SOURCES = ["unmold.hip"]
@@ -27,6 +29,10 @@ COCOEVAL_HEADERS = [os.path.join("..", "..", "include", "fi_cocoeval.h")]
 COCOMASK_LIB_PATH = os.path.join(_HERE, "libfi_cocomask.so")
 COCOMASK_SOURCES = ["cocomask.hip"]
 COCOMASK_HEADERS = [os.path.join("..", "..", "include", "fi_cocomask.h")]
+# the Sinkhorn term differentiated through its iterations (include/fi_ot.h): a fifth library, built the same way
+OT_LIB_PATH = os.path.join(_HERE, "libfi_ot.so")
+OT_SOURCES = ["sinkhorn_bp.hip"]
+OT_HEADERS = SINKHORN_HEADERS + [os.path.join("..", "..", "include", "fi_ot.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
@@ -55,6 +61,7 @@ def _compile(sources, headers, force, verbose):
     for s in srcs:
         o = s[:-4] + ".o"
         deps = [s] + hdrs + ([os.path.join(CSRC, "conv_bf16.hip")] if s.endswith("conv_f16.hip") else [])
+        deps += [os.path.join(CSRC, h) for h in SINKHORN_HEADERS] if s.endswith("sinkhorn.hip") else []
         if force or _stale(o, deps):
             cmd = [HIPCC] + FLAGS + ["-c", s, "-o", o]
             if verbose:
@@ -65,7 +72,8 @@ def _compile(sources, headers, force, verbose):
 
 
 def build_hip(force=False, verbose=False):
-    """Builds libfi_hip.so, libfi_eval.so, libfi_cocoeval.so and libfi_cocomask.so; returns the path of the first."""
+    """Builds libfi_hip.so, libfi_eval.so, libfi_cocoeval.so, libfi_cocomask.so and libfi_ot.so; returns the path of the
+    first."""
     objs = _compile(SOURCES, HEADERS, force, verbose)
     if force or _stale(LIB_PATH, objs):
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
@@ -74,7 +82,8 @@ def build_hip(force=False, verbose=False):
         subprocess.check_call(cmd)
     for lib, sources, headers in ((EVAL_LIB_PATH, EVAL_SOURCES, EVAL_HEADERS),
                                   (COCOEVAL_LIB_PATH, COCOEVAL_SOURCES, COCOEVAL_HEADERS),
-                                  (COCOMASK_LIB_PATH, COCOMASK_SOURCES, COCOMASK_HEADERS)):
+                                  (COCOMASK_LIB_PATH, COCOMASK_SOURCES, COCOMASK_HEADERS),
+                                  (OT_LIB_PATH, OT_SOURCES, OT_HEADERS)):
         objs = _compile(sources, HEADERS + headers, force, verbose)
         if force or _stale(lib, objs + [LIB_PATH]):
             cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + [

@@ -17,89 +17,12 @@
 // final <P, C> instead of being held in 64 more registers.  The roofline that
 // binds is on-chip (fp32 FMA issue + LDS/barrier latency); HBM traffic is 2*S*D
 // floats in and 1 float out per problem.
-#include "fi_common.h"
+// The device code (layout, LDS block, cost tile, reductions) is in sinkhorn_dev.h, which sinkhorn_bp.hip shares.
+#include "sinkhorn_dev.h"
 
 namespace {
 
-constexpr int kThreads = 1024;
-constexpr int kMaxS = 256;
-constexpr int kT = 8;         // tile edge held per thread
-constexpr int kDChunk = 16;   // feature columns staged per pass (D > 1)
-constexpr int kStride = 260;  // LDS row stride of the staged, transposed chunk
-#define FI_OT_EPS 1e-20f
-
-// v (DPP-moved) with zero where the control selects no source lane
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_mov(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xF, true));
-}
-
-struct Smem {
-    float a[kMaxS];
-    float b[kMaxS];
-    float nx[kMaxS];  // ||x_i|| + eps (cosine) -- divisor
-    float ny[kMaxS];
-    float red[16][kMaxS];
-    float xs[kDChunk][kStride];
-    float ys[kDChunk][kStride];
-    float wsum[16];
-};
-
-// cost tile C[r][c] for rows ti*8+r, cols tj*8+c of problem (x, y).
-__device__ void cost_tile(Smem &sm, const float *__restrict__ x, const float *__restrict__ y, int S,
-                          int D, int l2_cost, int normalize, int ti, int tj, float (&C)[kT][kT])
-{
-    const int tid = threadIdx.x;
-    float acc[kT][kT];
-#pragma unroll
-    for (int r = 0; r < kT; ++r)
-#pragma unroll
-        for (int c = 0; c < kT; ++c) acc[r][c] = 0.0f;
-
-    for (int d0 = 0; d0 < D; d0 += kDChunk) {
-        const int dc = min(kDChunk, D - d0);
-        __syncthreads();  // previous chunk fully consumed
-        for (int e = tid; e < kMaxS * kDChunk; e += kThreads) {
-            const int i = e / kDChunk;
-            const int d = e - i * kDChunk;
-            float xv = 0.0f, yv = 0.0f;
-            if (i < S && d < dc) {
-                xv = x[(size_t)i * D + d0 + d];
-                yv = y[(size_t)i * D + d0 + d];
-                if (normalize) {  // x /= (||x|| + eps), OT_module.py:111-112
-                    xv = xv / sm.nx[i];
-                    yv = yv / sm.ny[i];
-                }
-            }
-            sm.xs[d][i] = xv;
-            sm.ys[d][i] = yv;
-        }
-        __syncthreads();
-        for (int d = 0; d < dc; ++d) {
-            float xr[kT], yc[kT];
-#pragma unroll
-            for (int r = 0; r < kT; ++r) xr[r] = sm.xs[d][ti * kT + r];
-#pragma unroll
-            for (int c = 0; c < kT; ++c) yc[c] = sm.ys[d][tj * kT + c];
-#pragma unroll
-            for (int r = 0; r < kT; ++r)
-#pragma unroll
-                for (int c = 0; c < kT; ++c) {
-                    if (l2_cost) {
-                        const float df = xr[r] - yc[c];
-                        acc[r][c] = fmaf(df, df, acc[r][c]);
-                    } else {
-                        acc[r][c] = fmaf(xr[r], yc[c], acc[r][c]);
-                    }
-                }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < kT; ++r)
-#pragma unroll
-        for (int c = 0; c < kT; ++c) C[r][c] = l2_cost ? sqrtf(acc[r][c]) : (1.0f - acc[r][c]);
-}
+using namespace fi_ot_dev;
 
 __global__ __launch_bounds__(kThreads) void sinkhorn_kernel(const float *__restrict__ xs_all,
                                                             const float *__restrict__ ys_all, int S,
@@ -123,19 +46,7 @@ __global__ __launch_bounds__(kThreads) void sinkhorn_kernel(const float *__restr
 
     // ---- row norms (cosine) ----------------------------------------------------
     if (normalize) {
-        if (tid < 2 * kMaxS) {
-            const int i = tid & (kMaxS - 1);
-            const float *__restrict__ src = (tid < kMaxS) ? x : y;
-            float ss = 0.0f;
-            if (i < S)
-                for (int d = 0; d < D; ++d) {
-                    const float v = src[(size_t)i * D + d];
-                    ss = fmaf(v, v, ss);
-                }
-            const float nrm = sqrtf(ss) + FI_OT_EPS;
-            if (tid < kMaxS) sm.nx[i] = nrm; else sm.ny[i] = nrm;
-        }
-        __syncthreads();
+        row_norms(sm, x, y, S, D);
         if (xn_out && yn_out) {
             for (int e = tid; e < S * D; e += kThreads) {
                 const int i = e / D;
@@ -153,10 +64,8 @@ __global__ __launch_bounds__(kThreads) void sinkhorn_kernel(const float *__restr
 #pragma unroll
         for (int r = 0; r < kT; ++r)
 #pragma unroll
-            for (int c = 0; c < kT; ++c) {
-                const bool in = (ti * kT + r < S) && (tj * kT + c < S);
-                K[r][c] = in ? expf(-eps_inv * C[r][c]) : 0.0f;
-            }
+            for (int c = 0; c < kT; ++c)
+                K[r][c] = gibbs(C[r][c], eps_inv, (ti * kT + r < S) && (tj * kT + c < S));
     }
 
     const float u = 1.0f / (float)S;
@@ -167,84 +76,19 @@ __global__ __launch_bounds__(kThreads) void sinkhorn_kernel(const float *__restr
     __syncthreads();
 
     for (int it = 0; it < L; ++it) {
-        // ---- a = u / (K b + eps) ---------------------------------------------------
+        // ---- a = u / (K b + eps): row sums, one row and ONE division per lane (sinkhorn_dev.h, row_sum) ----
         {
-            float bv[kT];
-#pragma unroll
-            for (int c = 0; c < kT; ++c) bv[c] = sm.b[tj * kT + c];
-            float part[kT];
-#pragma unroll
-            for (int r = 0; r < kT; ++r) {
-                float s = 0.0f;
-#pragma unroll
-                for (int c = 0; c < kT; ++c) s = fmaf(K[r][c], bv[c], s);
-                part[r] = s;
-            }
-            // Reduce over the 32 lanes that share this row tile, HALVING the values a lane carries at every step: the pair
-            // (lane, partner) splits its rows -- the lower lane keeps the first half and is sent the partner's, the
-            // upper lane the second half -- so 8 values need 4 + 2 + 1 exchanges (quad_perm xor 1, xor 2, ds_swizzle xor 4: partners
-            // always carry the same rows), then the one value left is folded by row_ror:8 and ds_swizzle xor 16.
-            // Every lane ends with the FULL sum of one row, r = 4*bit0 + 2*bit1 + bit2 of its lane number, and does ONE
-            // division.  (Before: five DPP steps on all 8 values, the sums in lane 31 only, which then did 8 divisions
-            // one after the other -- under an exec mask, so at the full cost for the wavefront: 136 instructions, now ~40.)
-            float v4[4], v2[2], v;
-            {
-                const bool up = lane & 1;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float keep = up ? part[k + 4] : part[k], send = up ? part[k] : part[k + 4];
-                    v4[k] = keep + dpp_mov<0xB1, 0xF>(send);          // quad_perm [1,0,3,2]
-                }
-            }
-            {
-                const bool up = lane & 2;
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const float keep = up ? v4[k + 2] : v4[k], send = up ? v4[k] : v4[k + 2];
-                    v2[k] = keep + dpp_mov<0x4E, 0xF>(send);          // quad_perm [2,3,0,1]
-                }
-            }
-            {
-                const bool up = lane & 4;
-                const float keep = up ? v2[1] : v2[0], send = up ? v2[0] : v2[1];
-                v = keep + __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(send), 0x101F));   // lane ^ 4
-            }
-            v += dpp_mov<0x128, 0xF>(v);                              // row_ror:8 = lane ^ 8
-            v += __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), 0x401F));   // lane ^ 16
-            const int r = ((lane & 1) << 2) | (lane & 2) | ((lane >> 2) & 1);
-            const int i = ti * kT + r;
+            const float v = matvec_rows(K, sm.b, tj, lane);
+            const int i = ti * kT + row_of_lane(lane);
             const float ai = u / (v + FI_OT_EPS);
             if ((tj & 24) == 0 && i < S) sm.a[i] = ai;
         }
         __syncthreads();
-        // ---- b = u / (K^T a + eps) -------------------------------------------------
-        {
-            float av[kT];
-#pragma unroll
-            for (int r = 0; r < kT; ++r) av[r] = sm.a[ti * kT + r];
-            float part[kT];
-#pragma unroll
-            for (int c = 0; c < kT; ++c) {
-                float s = 0.0f;
-#pragma unroll
-                for (int r = 0; r < kT; ++r) s = fmaf(K[r][c], av[r], s);
-                part[c] = s;
-            }
-#pragma unroll
-            for (int c = 0; c < kT; ++c) {          // lane l + lane l^32 in every lane (v_permlane32_swap: no LDS crossbar)
-                const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_int(part[c]), __float_as_int(part[c]), false, false);
-                part[c] = __int_as_float(sw[0]) + __int_as_float(sw[1]);
-            }
-            if (lane < 32) {
-#pragma unroll
-                for (int c = 0; c < kT; ++c) sm.red[wave][tj * kT + c] = part[c];
-            }
-        }
+        // ---- b = u / (K^T a + eps): column sums through sm.red ------------------------
+        matvec_cols_stage(sm, K, sm.a, ti, tj, lane, wave);
         __syncthreads();
         if (tid < kMaxS) {
-            float s = 0.0f;
-#pragma unroll
-            for (int w = 0; w < 16; ++w) s += sm.red[w][tid];
+            const float s = col_sum(sm, tid);
             if (tid < S) sm.b[tid] = u / (s + FI_OT_EPS);
         }
         __syncthreads();
@@ -269,15 +113,7 @@ __global__ __launch_bounds__(kThreads) void sinkhorn_kernel(const float *__restr
             }
         }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) local += __shfl_xor(local, off, 64);
-    if (lane == 0) sm.wsum[wave] = local;
-    __syncthreads();
-    if (tid == 0) {
-        float s = 0.0f;
-        for (int w = 0; w < 16; ++w) s += sm.wsum[w];
-        loss[prob] = s;
-    }
+    block_sum_to(sm, local, lane, wave, loss + prob);
 }
 
 }  // namespace

@@ -50,7 +50,9 @@ class MaskRCNN(nn.Module):
         self.rpn = RPN(len(config.RPN.ANCHOR_RATIOS), config.RPN.ANCHOR_STRIDE, input_ch=256)
         self.dev_roi = Dev(config, depth=256)
         if config.DEV.SWITCH and config.DEV.LOSS_CHOICE == 'ot':
-            self.ot_loss = OptTrans(config, ch_x=1024, epsilon=config.DEV.OT_EPSILON, L=config.DEV.OT_L)
+            # DEV.OT_NO_BP_P_L = False: back-propagate through the Sinkhorn iterations (default: the detached plan)
+            self.ot_loss = OptTrans(config, ch_x=1024, epsilon=config.DEV.OT_EPSILON, L=config.DEV.OT_L,
+                                    no_bp_P_L=getattr(config.DEV, "OT_NO_BP_P_L", True))
         self.classifier = Classifier(depth=256, num_classes=config.DATASET.NUM_CLASSES,
                                      pool_size=config.MRCNN.POOL_SIZE, config=config)
         self.mask = Mask(depth=256, num_classes=config.DATASET.NUM_CLASSES)
