@@ -1,6 +1,7 @@
-// conv3x3_wino.hip -- Winograd F(2x2,3x3) form of the 3x3 / stride 1 / pad 1 convolution on 14 x 14 maps (forward and
-// data gradient of the mask head's 256 -> 256 layers) for gfx950.  Reached from fi_conv2d_forward_live when plan_forward
-// (csrc/conv_igemm.hip) sets FwdPlan::wino; it runs in the conv3x3_patch_flat slot and shares its profiling counter.
+// conv3x3_wino.hip -- Winograd F(2x2,3x3) form of the 3x3 / stride 1 / pad 1 convolution on NCHW maps with even H and W
+// (forward and data gradient: the mask head's 14 x 14 layers, and the backbone / FPN / RPN layers on 2-D maps) for gfx950.
+// Reached from fi_conv2d_forward_live when plan_forward (csrc/conv_igemm.hip) sets FwdPlan::wino; it runs in the
+// conv3x3_patch_flat slot (14 x 14) or the conv3x3_patch slot (W % 16 == 0) and shares the slot's profiling counter.
 #include <stdint.h>
 
 #include "fi_common.h"
@@ -21,18 +22,19 @@ struct Epilogue {
 };
 
 struct WinoGeom {
-    int N, Cin, Cout;
+    int N, Cin, H, W, Cout;
     int flip;            // taps applied in reverse order (data gradient)
     int ptiles, mtiles;  // groups of WN_GROUP tiles, Cout tiles
     const float *zero;
 };
 
 // -------------------------------------------------------------------------------------
-// 3x3 / stride 1 / pad 1 on 14 x 14 maps: Winograd F(2x2,3x3), 16 MFMAs where the direct form needs 36
+// 3x3 / stride 1 / pad 1 on maps with even H and W: Winograd F(2x2,3x3), 16 MFMAs where the direct form needs 36
 // -------------------------------------------------------------------------------------
-// Y = At [ (G g Gt) . (Bt d B) ] A per 2x2 output tile: a 14 x 14 map is exactly 7 x 7 tiles whose 4 x 4 input windows
+// Y = At [ (G g Gt) . (Bt d B) ] A per 2x2 output tile: an H x W map is exactly H/2 x W/2 tiles whose 4 x 4 input windows
 // start at (2ty - 1, 2tx - 1), so no tile is ragged and only the outermost window row / column is padding.  A workgroup
-// owns 32 CONSECUTIVE tiles of the flattened (image, tile row, tile column) space x 128 output channels (4 wavefronts
+// owns 32 CONSECUTIVE tiles of the flattened (image, tile row, tile column) space (on a map of 64 or more tiles per row:
+// 2 output rows x 64 columns; on narrow maps a group wraps rows and spans images) x 128 output channels (4 wavefronts
 // x 32); a wavefront keeps the 16 transform-domain accumulators of its 32 x 32 block (256 registers: one wavefront per
 // SIMD).  Per block of 16 input channels:
 //   V = Bt d B  is computed ONCE per workgroup on the way into LDS (a thread: one tile x two channels, 16 clamped
@@ -48,7 +50,6 @@ struct WinoGeom {
 // 128 MFMAs per wavefront and channel block (direct: 288).  An accumulator is a chain over the channels in a fixed
 // order (block by block, pair (k, k + 8) by pair) and the output transform is lane-local, so an output element's
 // arithmetic does not depend on the tile's place in its group or in the batch.
-constexpr int WN_HW = fi::WINO_HW, WN_T = WN_HW / 2;                 // map size, tiles per row / column
 constexpr int WN_GROUP = 32;                        // tiles per workgroup
 constexpr int WN_TP = 20;                           // floats per tile of V: 16 lanes x 16 bytes at this pitch cover the 64 banks once
 constexpr int WN_CP = WN_GROUP * WN_TP;             // floats per channel of V
@@ -58,9 +59,9 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 // the compiler reads all 256 sums out of the accumulator registers in front of the branch and spills): an absent
 // residual / gate is loaded from the page of zeros (stride 0) and selected away.
 __device__ __forceinline__ void wino_epilogue(const f32x16 (&acc)[16], const Epilogue &ep, float *__restrict__ y, size_t obase,
-                                              bool tile_ok, int mb, int Cout, const float *__restrict__ zero)
+                                              bool tile_ok, int mb, int Cout, const float *__restrict__ zero, int W,
+                                              size_t HW)
 {
-    constexpr size_t HW = WN_HW * WN_HW;
     const bool has_sc = ep.scale != nullptr, has_bi = ep.bias != nullptr, relu = ep.relu != 0;
     const bool has_res = ep.residual != nullptr, has_gate = ep.gate != nullptr;
     const float *__restrict__ sp = has_sc ? ep.scale : zero;
@@ -77,9 +78,9 @@ __device__ __forceinline__ void wino_epilogue(const f32x16 (&acc)[16], const Epi
         const size_t o = obase + (size_t)mrow * HW;
         const float sc = sp[(mb + mrow) * smul], bi = bp[(mb + mrow) * bmul];
         const float2 r0 = *reinterpret_cast<const float2 *>(rp + o * rmul);
-        const float2 r1 = *reinterpret_cast<const float2 *>(rp + (o + WN_HW) * rmul);
+        const float2 r1 = *reinterpret_cast<const float2 *>(rp + (o + W) * rmul);
         const float2 g0 = *reinterpret_cast<const float2 *>(gp + o * gmul);
-        const float2 g1 = *reinterpret_cast<const float2 *>(gp + (o + WN_HW) * gmul);
+        const float2 g1 = *reinterpret_cast<const float2 *>(gp + (o + W) * gmul);
         // At M A: rows first (p[i][0] = m_i0 + m_i1 + m_i2, p[i][1] = m_i1 - m_i2 - m_i3), then columns
         float p[4][2];
 #pragma unroll
@@ -105,12 +106,14 @@ __device__ __forceinline__ void wino_epilogue(const f32x16 (&acc)[16], const Epi
         }
         if (tile_ok && row_ok) {
             *reinterpret_cast<float2 *>(y + o) = make_float2(t[0], t[1]);
-            *reinterpret_cast<float2 *>(y + o + WN_HW) = make_float2(t[2], t[3]);
+            *reinterpret_cast<float2 *>(y + o + W) = make_float2(t[2], t[3]);
         }
     }
 }
 
-// H == W == 14, Cin % 16 == 0 (plan_forward)
+// H and W even, Cin % 16 == 0 (plan_forward).  FIX: H == W == FIX at compile time (the 14 x 14 RoI maps: the tile decode and
+// the strides fold to constants), 0: H and W from g.
+template <int FIX>
 __global__ __launch_bounds__(kThreads, 1) void conv3x3_wino_flat_kernel(const float *__restrict__ x,
                                                                        const float *__restrict__ w, Epilogue ep,
                                                                        float *__restrict__ y, WinoGeom g)
@@ -124,8 +127,10 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_wino_flat_kernel(const fl
     const int pt = xcd * per_xcd + local / g.mtiles;
     if (pt >= g.ptiles) return;
     const int m0 = mt * 128;
-    const int ntiles = g.N * (WN_T * WN_T);
-    constexpr int HW = WN_HW * WN_HW;
+    const int H = FIX ? FIX : g.H, W = FIX ? FIX : g.W;
+    const int TX = W / 2, TT = (H / 2) * TX;                         // tiles per row, per image
+    const int HW = H * W;
+    const int ntiles = g.N * TT;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
@@ -137,17 +142,17 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_wino_flat_kernel(const fl
     const int s_t = pt * WN_GROUP + (tid & 31);
     const bool s_ok = s_t < ntiles;
     const int s_tc = s_ok ? s_t : 0;
-    const int s_n = s_tc / (WN_T * WN_T), s_rem = s_tc - s_n * (WN_T * WN_T);
-    const int s_ty = s_rem / WN_T, s_tx = s_rem - s_ty * WN_T;
+    const int s_n = s_tc / TT, s_rem = s_tc - s_n * TT;
+    const int s_ty = s_rem / TX, s_tx = s_rem - s_ty * TX;
     int s_ro[4], s_co[4];
     bool s_rok[4], s_cok[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int yy = 2 * s_ty - 1 + r, xx = 2 * s_tx - 1 + r;
-        s_rok[r] = s_ok && yy >= 0 && yy < WN_HW;
-        s_cok[r] = xx >= 0 && xx < WN_HW;
-        s_ro[r] = min(max(yy, 0), WN_HW - 1) * WN_HW;
-        s_co[r] = min(max(xx, 0), WN_HW - 1);
+        s_rok[r] = s_ok && yy >= 0 && yy < H;
+        s_cok[r] = xx >= 0 && xx < W;
+        s_ro[r] = min(max(yy, 0), H - 1) * W;
+        s_co[r] = min(max(xx, 0), W - 1);
     }
     const int s_base = (s_n * g.Cin + (tid >> 5)) * HW;              // < 2^31 (patch_eligible)
     float raw[2][16];
@@ -332,10 +337,10 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_wino_flat_kernel(const fl
     const int o_t = pt * WN_GROUP + l31;
     const bool tile_ok = o_t < ntiles;
     const int o_tc = tile_ok ? o_t : 0;
-    const int o_n = o_tc / (WN_T * WN_T), o_rem = o_tc - o_n * (WN_T * WN_T);
-    const int o_ty = o_rem / WN_T, o_tx = o_rem - o_ty * WN_T;
-    const size_t obase = ((size_t)o_n * g.Cout + mb) * HW + (size_t)(2 * o_ty) * WN_HW + 2 * o_tx;
-    wino_epilogue(acc, ep, y, obase, tile_ok, mb, g.Cout, g.zero);
+    const int o_n = o_tc / TT, o_rem = o_tc - o_n * TT;
+    const int o_ty = o_rem / TX, o_tx = o_rem - o_ty * TX;
+    const size_t obase = ((size_t)o_n * g.Cout + mb) * HW + (size_t)(2 * o_ty) * W + 2 * o_tx;
+    wino_epilogue(acc, ep, y, obase, tile_ok, mb, g.Cout, g.zero, W, (size_t)HW);
 }
 
 }  // namespace
@@ -345,14 +350,17 @@ namespace fi {
 void launch_conv3x3_wino_flat(const WinoArgs &a, hipStream_t st)
 {
     WinoGeom g;
-    g.N = a.N; g.Cin = a.Cin; g.Cout = a.Cout;
+    g.N = a.N; g.Cin = a.Cin; g.H = a.H; g.W = a.W; g.Cout = a.Cout;
     g.flip = a.flip;
-    g.ptiles = ceil_div(a.N * WN_T * WN_T, WN_GROUP);
+    g.ptiles = ceil_div(a.N * (a.H / 2) * (a.W / 2), WN_GROUP);
     g.mtiles = ceil_div(a.Cout, 128);
     g.zero = a.zero;
     const Epilogue ep = {a.bias, a.scale, a.residual, a.relu, a.gate};
     const long blocks = (long)ceil_div(g.ptiles, 8) * 8 * g.mtiles;
-    hipLaunchKernelGGL(conv3x3_wino_flat_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, a.x, a.w, ep, a.y, g);
+    if (a.H == WINO_HW && a.W == WINO_HW)
+        hipLaunchKernelGGL(conv3x3_wino_flat_kernel<WINO_HW>, dim3((unsigned)blocks), dim3(kThreads), 0, st, a.x, a.w, ep, a.y, g);
+    else
+        hipLaunchKernelGGL(conv3x3_wino_flat_kernel<0>, dim3((unsigned)blocks), dim3(kThreads), 0, st, a.x, a.w, ep, a.y, g);
 }
 
 }  // namespace fi

@@ -2046,7 +2046,7 @@ struct FwdPlan {
     FwdPath path;
     bool bm64;        // FWD_GENERIC: 64-row tiles (128 otherwise)
     bool hwc;         // tap-major weights: the fast gather path
-    bool wino;        // FWD_PATCH_FLAT: the Winograd F(2x2,3x3) form (conv3x3_wino_flat_kernel); same counter
+    bool wino;        // FWD_PATCH / FWD_PATCH_FLAT: the Winograd F(2x2,3x3) form (conv3x3_wino_flat_kernel); same counter
     int kernel_id;    // FI_K_*: the profiling counter of the launch
 };
 
@@ -2102,6 +2102,15 @@ int plan_forward(ConvGeom &g, FwdPlan &p, const float *x, const float *weight, c
         // 14 x 14 maps (7 x 7 Winograd tiles, none ragged) with at least 4 channel blocks: 2.25x fewer MFMAs.  The
         // launch fills the chip by the flat kernel's own rule (patch == 2); FI_NO_WINOGRAD keeps the direct form.
         p.wino = patch == 2 && H == fi::WINO_HW && W == fi::WINO_HW && Cin % BK == 0 && Cin >= 64 && !getenv("FI_NO_WINOGRAD");
+        // 2-D maps (patch == 1) with even H: the same kernel with H and W at run time -- NCHW output only, y / residual /
+        // gate 8-byte aligned for the float2 accesses of its epilogue (by alignment, never by presence).  Every grid size
+        // of the rule is taken: interleaved with the direct kernel (scripts/patch_probe.py, profiles/wino2d_probe.txt,
+        // medians of 5 rounds, spread under 1 %) it is 1.45x faster at 256 workgroups (64 x 64, 256 -> 256, N 4), 1.32x
+        // at 512 (128 x 128, 128 -> 128), 1.42x at 1024, 1.41x at 2048, 1.36x at 4096 and 1.36x at 8192 (256 x 256,
+        // 256 -> 512).  Below the rule's 256 workgroups the layer stays on conv_fwd_kernel.
+        if (patch == 1 && H % 2 == 0 && Cin % BK == 0 && Cin >= 64 && !g.out_nhwc && (uintptr_t)y % 8 == 0 &&
+            (uintptr_t)residual % 8 == 0 && (uintptr_t)gate % 8 == 0 && !getenv("FI_NO_WINOGRAD"))
+            p.wino = true;
     } else if (reg1x1) {
         p.path = FWD_REG1X1;
         p.kernel_id = FI_K_CONV1X1_REG;
@@ -2481,8 +2490,8 @@ int fi_conv2d_forward_live(const float *x, const float *weight, const float *bia
         FI_HIP_CHECK(hipGetLastError());
         return FI_OK;
     }
-    if (plan.path == FWD_PATCH_FLAT && plan.wino) {
-        const fi::WinoArgs wa = {x, weight, bias, scale, residual, gate, y, g.zero, N, Cin, Cout, relu, g.flip};
+    if ((plan.path == FWD_PATCH || plan.path == FWD_PATCH_FLAT) && plan.wino) {
+        const fi::WinoArgs wa = {x, weight, bias, scale, residual, gate, y, g.zero, N, Cin, H, W, Cout, relu, g.flip};
         fi::launch_conv3x3_wino_flat(wa, st);
         FI_HIP_CHECK(hipGetLastError());
         return FI_OK;

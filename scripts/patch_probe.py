@@ -26,14 +26,15 @@ run("mask 14x14 256 N1376", 1376, 256, 14, 14, 256, "conv3x3_patch_flat")
 run("mask 14x14 256 N672", 672, 256, 14, 14, 256, "conv3x3_patch_flat")
 
 
-def run_flat(name, N, Cin, Cout=256, rounds=5, iters=8):
-    """The flat slot with its Winograd form and with FI_NO_WINOGRAD=1 (the library reads the switch per call), rounds of
-    the two interleaved in this process on the same random data: median and min us per variant, TFLOP/s in direct-form
-    flops (the Winograd form issues 16/36 of the MFMAs, so its figure may read above the MFMA peak)."""
-    x = torch.randn(N, Cin, 14, 14, device=DEV)
+def run_flat(name, N, Cin, Cout=256, H=14, W=14, key="conv3x3_patch_flat", rounds=5, iters=8):
+    """A patch slot (flat or 2-D) with its Winograd form and with FI_NO_WINOGRAD=1 (the library reads the switch per call),
+    rounds of the two interleaved in this process on the same random data: median and min us per variant, TFLOP/s in
+    direct-form flops (the Winograd form issues 16/36 of the MFMAs, so its figure may read above the MFMA peak).  On a shape
+    the planner keeps on the direct kernel the two variants are the same launch and the speed-up reads 1."""
+    x = torch.randn(N, Cin, H, W, device=DEV)
     w = (torch.randn(Cout, Cin, 3, 3, device=DEV) * 0.05).contiguous(memory_format=torch.channels_last)
     sc = torch.rand(Cout, device=DEV) + 0.5; b = torch.randn(Cout, device=DEV)
-    key = "conv3x3_patch_flat"; us = {"winograd": [], "direct": []}
+    us = {"winograd": [], "direct": []}
     for r in range(rounds + 1):
         for variant in ("winograd", "direct"):
             if variant == "direct": os.environ["FI_NO_WINOGRAD"] = "1"
@@ -44,7 +45,7 @@ def run_flat(name, N, Cin, Cout=256, rounds=5, iters=8):
             n, ms = _lib.prof_get(key); assert n == iters, (n, iters)
             if r: us[variant].append(ms / n * 1e3)                 # round 0 warms up
     os.environ.pop("FI_NO_WINOGRAD", None)
-    fl = 2.0 * N * 196 * Cin * Cout * 9; out = {"layer": name}
+    fl = 2.0 * N * H * W * Cin * Cout * 9; out = {"layer": name}
     for variant, v in us.items():
         v.sort(); med = v[len(v) // 2]
         out[variant] = {"us_median": round(med, 1), "us_min": round(v[0], 1), "TFLOPs_direct_form": round(fl / med / 1e6, 1)}
@@ -55,3 +56,11 @@ def run_flat(name, N, Cin, Cout=256, rounds=5, iters=8):
 for n_img in (1376, 672):
     for cin in (256, 128, 64):
         run_flat("mask 14x14 %d->256 N%d" % (cin, n_img), n_img, cin)
+# the 2-D slot, one line per grid size of a batch-4 step at 1024 x 1024 (workgroups of the direct kernel in brackets)
+for name, N, Cin, H, W, Cout in (("C4 / P4 64x64 256->256 N4 (256)", 4, 256, 64, 64, 256),
+                                 ("C3 128x128 128->128 N4 (512)", 4, 128, 128, 128, 128),
+                                 ("P3 128x128 256->256 N4 (1024)", 4, 256, 128, 128, 256),
+                                 ("RPN P3 128x128 256->512 N4 (2048)", 4, 256, 128, 128, 512),
+                                 ("FPN P2 256x256 256->256 N4 (4096)", 4, 256, 256, 256, 256),
+                                 ("RPN P2 256x256 256->512 N4 (8192)", 4, 256, 256, 256, 512)):
+    run_flat(name, N, Cin, Cout, H, W, key="conv3x3_patch")
