@@ -22,6 +22,17 @@ c_char_p = ctypes.c_char_p
 _pp = ctypes.POINTER(ctypes.c_void_p)
 _ip = ctypes.POINTER(ctypes.c_int)
 
+
+
+class ConvLaunch(ctypes.Structure):
+    """FiConvLaunch of include/fi_capi.h: one planned launch of the fp32 convolution kernels."""
+    _fields_ = [(f, ctypes.c_int32) for f in (
+        "form", "kernel_id", "tile_rows", "tile_pixels", "window", "flags", "grid_x", "grid_y", "grid_z", "p_base", "pixels",
+        "splits", "pixels_per_split", "per_launch")]
+
+
+_lp = ctypes.POINTER(ConvLaunch)
+
 # name -> (restype, argtypes); mirrors include/fi_capi.h one to one
 SIGNATURES = {
     "fi_version": (c_char_p, []),
@@ -115,6 +126,9 @@ SIGNATURES = {
     "fi_conv2d_weight_grad_plan_bf16": (c_int, [c_void_p] * 4 + [c_int] * 13 + [_ip, _ip]),
     "fi_conv2d_weight_grad_plan_f16": (c_int, [c_void_p] * 4 + [c_int] * 13 + [_ip, _ip]),
     "fi_gemm_nt_plan": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p, _ip]),
+    "fi_conv2d_forward_launches": (c_int, [c_void_p] * 7 + [c_int] * 16 + [_lp, _ip]),
+    "fi_conv2d_weight_grad_launch": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 12 + [c_void_p, c_int, c_int, _lp]),
+    "fi_gemm_nt_launch": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p, _lp]),
     "fi_weight_transpose_batch": (c_int, [c_void_p, c_int, ctypes.c_long, c_void_p]),
     "fi_conv3x3_forward_bf16w": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p]),
     "fi_conv1x1_forward_bf16w": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
@@ -190,6 +204,22 @@ def planned_kernel(query, *args):
     k = ctypes.c_int(-1)
     check(query(*args, ctypes.byref(k)), "kernel plan query")
     return KERNEL_KEYS[k.value]
+
+
+# FI_FWD_* / FI_WGRAD_* / FI_WIN_* by value and the FI_LAUNCH_* flag bits of include/fi_capi.h
+FWD_FORMS = ("GENERIC", "PATCH", "PATCH_FLAT13", "PATCH_FLAT14", "WINO14", "WINO", "REG1X1", "RING")
+WGRAD_FORMS = ("VEC", "VEC_TWO_TAP", "SCALAR_TAP_MAJOR", "SCALAR_ROW_MAJOR")
+WINDOWS = ("1x1", "3x3", "7x7", "other")
+LAUNCH_FLAGS = {"tap_major": 1, "channels_last": 2, "vec_out": 4, "swizzled": 8, "row_uniform": 16}
+
+
+def planned_launches(query, *args):
+    """The ConvLaunch list of a launch entry: `query` is fi_conv2d_forward_launches (one or two launches),
+    fi_conv2d_weight_grad_launch or fi_gemm_nt_launch (one), `args` its arguments up to the descriptors it writes."""
+    out, n = (ConvLaunch * 2)(), ctypes.c_int(1)
+    tail = (ctypes.byref(n),) if query.__name__ == "fi_conv2d_forward_launches" else ()
+    check(query(*args, out, *tail), "launch plan query")
+    return list(out[:n.value])
 
 
 def conv16_variant(query, *args):

@@ -50,7 +50,7 @@ struct WinoGeom {
 // 128 MFMAs per wavefront and channel block (direct: 288).  An accumulator is a chain over the channels in a fixed
 // order (block by block, pair (k, k + 8) by pair) and the output transform is lane-local, so an output element's
 // arithmetic does not depend on the tile's place in its group or in the batch.
-constexpr int WN_GROUP = 32;                        // tiles per workgroup
+constexpr int WN_GROUP = fi::WINO_GROUP;                       // tiles per workgroup
 constexpr int WN_TP = 20;                           // floats per tile of V: 16 lanes x 16 bytes at this pitch cover the 64 banks once
 constexpr int WN_CP = WN_GROUP * WN_TP;             // floats per channel of V
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
@@ -356,11 +356,8 @@ void launch_conv3x3_wino_flat(const WinoArgs &a, hipStream_t st)
     g.mtiles = ceil_div(a.Cout, 128);
     g.zero = a.zero;
     const Epilogue ep = {a.bias, a.scale, a.residual, a.relu, a.gate};
-    const long blocks = (long)ceil_div(g.ptiles, 8) * 8 * g.mtiles;
-    if (a.H == WINO_HW && a.W == WINO_HW)
-        hipLaunchKernelGGL(conv3x3_wino_flat_kernel<WINO_HW>, dim3((unsigned)blocks), dim3(kThreads), 0, st, a.x, a.w, ep, a.y, g);
-    else
-        hipLaunchKernelGGL(conv3x3_wino_flat_kernel<0>, dim3((unsigned)blocks), dim3(kThreads), 0, st, a.x, a.w, ep, a.y, g);
+    auto k = a.hw14 ? conv3x3_wino_flat_kernel<WINO_HW> : conv3x3_wino_flat_kernel<0>;
+    hipLaunchKernelGGL(k, dim3((unsigned)a.grid), dim3(kThreads), 0, st, a.x, a.w, ep, a.y, g);
 }
 
 }  // namespace fi

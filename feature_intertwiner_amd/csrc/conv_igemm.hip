@@ -1875,185 +1875,118 @@ int make_geom(ConvGeom &g, int N, int Cin, int H, int W, int Cout, int R, int S,
     return FI_OK;
 }
 
-template <int BM>
-void launch_fwd(const ConvGeom &g_in, const float *x, const float *w, const Epilogue &ep, float *y,
-                bool hwc, hipStream_t st)
+// window class (FI_WIN_*) -> instantiation.  7x7 exists only with row-major weights, 1x1 only with tap-major ones: the
+// planners name FI_WIN_OTHER (R and S at run time) for the rest.
+template <int BM, bool HWC, bool ONHWC = false, int BNT = BN>
+auto fwd_kernel_for(int win)
 {
-    ConvGeom g = g_in;
-    g.vec_out = (!g.out_nhwc && (g.OH * g.OW) % 4 == 0 && ((uintptr_t)y % 16 == 0) &&
-                 (ep.residual == nullptr || (uintptr_t)ep.residual % 16 == 0) &&
-                 (ep.gate == nullptr || (uintptr_t)ep.gate % 16 == 0)) ? 1 : 0;
-    // 64-pixel tiles when even 64-row tiles leave fewer than 4 workgroups per CU (C4/C5 of the backbone
-    // at batch 4): twice the workgroups, so that 4 wavefronts share each SIMD's MFMA pipe
-    if constexpr (BM == 64) {
-        const long wgs = (long)fi::ceil_div(g.P, BN) * fi::ceil_div(g.Cout, BM);
-        if (hwc && !g.out_nhwc && wgs < 1024 && g.P >= 64) {
-            dim3 grid64(fi::ceil_div(g.P, 64), fi::ceil_div(g.Cout, BM));
-            if (g.R == 3 && g.S == 3)
-                hipLaunchKernelGGL((conv_fwd_kernel<64, 3, 3, true, false, 64>), grid64, dim3(kThreads), 0, st, x, w, ep, y, g);
-            else if (g.R == 1 && g.S == 1)
-                hipLaunchKernelGGL((conv_fwd_kernel<64, 1, 1, true, false, 64>), grid64, dim3(kThreads), 0, st, x, w, ep, y, g);
-            else
-                hipLaunchKernelGGL((conv_fwd_kernel<64, 0, 0, true, false, 64>), grid64, dim3(kThreads), 0, st, x, w, ep, y, g);
-            return;
-        }
+    if (win == FI_WIN_3X3) return &conv_fwd_kernel<BM, 3, 3, HWC, ONHWC, BNT>;
+    if constexpr (HWC) {
+        if (win == FI_WIN_1X1) return &conv_fwd_kernel<BM, 1, 1, HWC, ONHWC, BNT>;
+    } else {
+        if (win == FI_WIN_7X7) return &conv_fwd_kernel<BM, 7, 7, HWC, ONHWC, BNT>;
     }
-    // Tail launch.  All tiles of a layer cost the same, so a grid of r.f "rounds" of the 1024 resident
-    // workgroups ends with a round that uses a fraction f of the chip (mask head: 6272 tiles = 6.125
-    // rounds).  A small remainder is cut off and run as 64x64 tiles -- 4x the workgroups, a quarter of the
-    // work each -- so that it spreads over all CUs.
-    if constexpr (BM == 128) {
-        const long ny = fi::ceil_div(g.Cout, BM);
-        const long nx_all = fi::ceil_div(g.P, BN);
-        const long wgs = nx_all * ny, slots = 1024;
-        const long rem = wgs % slots;
-        if (hwc && !g.out_nhwc && g.p_base == 0 && wgs > slots && rem > 0 && rem * 3 < slots && slots % ny == 0) {
-            const long nx_main = (wgs / slots) * (slots / ny);
-            ConvGeom gm = g, gt = g;
-            gm.P = (int)(nx_main * BN);
-            launch_fwd<128>(gm, x, w, ep, y, hwc, st);          // p_base == 0, wgs % slots == 0: no recursion
-            gt.p_base = gm.P;
-            dim3 grid64(fi::ceil_div(g.P - gm.P, 64), fi::ceil_div(g.Cout, 64));
-            if (g.R == 3 && g.S == 3)
-                hipLaunchKernelGGL((conv_fwd_kernel<64, 3, 3, true, false, 64>), grid64, dim3(kThreads), 0, st, x, w, ep, y, gt);
-            else if (g.R == 1 && g.S == 1)
-                hipLaunchKernelGGL((conv_fwd_kernel<64, 1, 1, true, false, 64>), grid64, dim3(kThreads), 0, st, x, w, ep, y, gt);
-            else
-                hipLaunchKernelGGL((conv_fwd_kernel<64, 0, 0, true, false, 64>), grid64, dim3(kThreads), 0, st, x, w, ep, y, gt);
-            return;
-        }
-    }
-    int nx = fi::ceil_div(g.P, BN);
-    // XCD-aware order for large compute-bound grids; short-K 1x1 layers are bound by their output
-    // stream and small grids by occupancy -- both measured faster in the plain order
-    // (not with a device-side live count: the live tiles are the FIRST ones, and a band per XCD would hand them all to one
-    // or two XCDs)
-    if (nx >= 512 && (g.R * g.S > 1 || g.K >= 128) && !g.n_live) {
-        g.swz = 1;
-        nx = fi::ceil_div(nx, 8) * 8;
-    }
-    dim3 grid(nx, fi::ceil_div(g.Cout, BM));
-    if (hwc && g.out_nhwc) {
-        if (g.R == 3 && g.S == 3)
-            hipLaunchKernelGGL((conv_fwd_kernel<BM, 3, 3, true, true>), grid, dim3(kThreads), 0, st, x, w, ep, y, g);
-        else if (g.R == 1 && g.S == 1)
-            hipLaunchKernelGGL((conv_fwd_kernel<BM, 1, 1, true, true>), grid, dim3(kThreads), 0, st, x, w, ep, y, g);
-        else
-            hipLaunchKernelGGL((conv_fwd_kernel<BM, 0, 0, true, true>), grid, dim3(kThreads), 0, st, x, w, ep, y, g);
-        return;
-    }
-    if (hwc) {
-        if (g.R == 3 && g.S == 3)
-            hipLaunchKernelGGL((conv_fwd_kernel<BM, 3, 3, true>), grid, dim3(kThreads), 0, st, x, w, ep, y, g);
-        else if (g.R == 1 && g.S == 1)
-            hipLaunchKernelGGL((conv_fwd_kernel<BM, 1, 1, true>), grid, dim3(kThreads), 0, st, x, w, ep, y, g);
-        else
-            hipLaunchKernelGGL((conv_fwd_kernel<BM, 0, 0, true>), grid, dim3(kThreads), 0, st, x, w, ep, y, g);
-        return;
-    }
-    if (g.R == 3 && g.S == 3)
-        hipLaunchKernelGGL((conv_fwd_kernel<BM, 3, 3, false>), grid, dim3(kThreads), 0, st, x, w, ep, y, g);
-    else if (g.R == 7 && g.S == 7)
-        hipLaunchKernelGGL((conv_fwd_kernel<BM, 7, 7, false>), grid, dim3(kThreads), 0, st, x, w, ep, y, g);
-    else
-        hipLaunchKernelGGL((conv_fwd_kernel<BM, 0, 0, false>), grid, dim3(kThreads), 0, st, x, w, ep, y, g);
+    return &conv_fwd_kernel<BM, 0, 0, HWC, ONHWC, BNT>;
+}
+
+template <int BM>
+auto fwd_kernel_for(const FiConvLaunch &l)
+{
+    if (l.flags & FI_LAUNCH_CHANNELS_LAST) return fwd_kernel_for<BM, true, true>(l.window);
+    return (l.flags & FI_LAUNCH_TAP_MAJOR) ? fwd_kernel_for<BM, true>(l.window) : fwd_kernel_for<BM, false>(l.window);
+}
+
+// one planned launch of conv_fwd_kernel (FI_FWD_GENERIC): a whole layer, or the main / tail part of one
+void launch_fwd(const FiConvLaunch &l, ConvGeom g, const float *x, const float *w, const Epilogue &ep, float *y,
+                hipStream_t st)
+{
+    g.vec_out = (l.flags & FI_LAUNCH_VEC_OUT) ? 1 : 0;
+    g.swz = (l.flags & FI_LAUNCH_SWIZZLED) ? 1 : 0;
+    g.p_base = l.p_base;
+    g.P = l.p_base + l.pixels;
+    auto k = l.tile_pixels == 64 ? fwd_kernel_for<64, true, false, 64>(l.window)
+                                 : (l.tile_rows == 64 ? fwd_kernel_for<64>(l) : fwd_kernel_for<128>(l));
+    hipLaunchKernelGGL(k, dim3(l.grid_x, l.grid_y), dim3(kThreads), 0, st, x, w, ep, y, g);
 }
 
 // same-size stride-1 layers (every 3x3/pad-1 and 1x1 layer of the model) can use the row-major kernel
 bool wgrad_same_size(const ConvGeom &g, const float *x, const float *dy)
 {
     return g.sh == 1 && g.sw == 1 && g.OH == g.H && g.OW == g.W && (g.H * g.W) % 4 == 0 && g.W >= 4 &&
-           (size_t)g.N * g.Cin * g.H * g.W * 4 < 0x7fffff00ULL &&
-           (size_t)g.N * g.Cout * g.H * g.W * 4 < 0x7fffff00ULL && ((uintptr_t)x % 16 == 0) &&
-           ((uintptr_t)dy % 16 == 0);
+           (size_t)g.N * g.Cin * g.H * g.W * 4 < 0x7fffff00ULL && (size_t)g.N * g.Cout * g.H * g.W * 4 < 0x7fffff00ULL &&
+           ((uintptr_t)x % 16 == 0) && ((uintptr_t)dy % 16 == 0);
 }
 
-template <int BM>
-void launch_wgrad(const ConvGeom &g, const float *x, const float *dy, float *dw, int splits,
-                  int p_per_split, bool hwc, float *dbias, hipStream_t st, const WgradBatch *batch = nullptr)
+template <int BM, bool HALF>
+auto wgrad_vec_kernel_for(int win, bool u16)
 {
-    dim3 grid(fi::ceil_div(g.K, BN), fi::ceil_div(g.Cout, BM), splits);
-    const bool same = wgrad_same_size(g, x, dy);
+    if (win == FI_WIN_3X3) return u16 ? &conv_wgrad_vec_kernel<BM, 3, 3, HALF, true> : &conv_wgrad_vec_kernel<BM, 3, 3, HALF>;
+    if (win == FI_WIN_1X1) return u16 ? &conv_wgrad_vec_kernel<BM, 1, 1, HALF, true> : &conv_wgrad_vec_kernel<BM, 1, 1, HALF>;
+    return &conv_wgrad_vec_kernel<BM, 0, 0, HALF>;
+}
+
+template <int BM, bool HWC>
+auto wgrad_kernel_for(int win)
+{
+    if (win == FI_WIN_3X3) return &conv_wgrad_kernel<BM, 3, 3, HWC>;
+    if (win == FI_WIN_1X1) return &conv_wgrad_kernel<BM, 1, 1, HWC>;
+    if constexpr (!HWC) {
+        if (win == FI_WIN_7X7) return &conv_wgrad_kernel<BM, 7, 7, HWC>;
+    }
+    return &conv_wgrad_kernel<BM, 0, 0, HWC>;
+}
+
+// the planned launch of a weight gradient (or of fi_gemm_nt's product)
+template <int BM>
+void launch_wgrad_bm(const FiConvLaunch &l, ConvGeom g, const float *x, const float *dy, float *dw, float *dbias,
+                     hipStream_t st, const WgradBatch *batch)
+{
+    dim3 grid(l.grid_x, l.grid_y, l.grid_z);
+    const int pps = l.pixels_per_split;
+    if (l.form == FI_WGRAD_SCALAR_TAP_MAJOR || l.form == FI_WGRAD_SCALAR_ROW_MAJOR) {
+        auto k = l.form == FI_WGRAD_SCALAR_TAP_MAJOR ? wgrad_kernel_for<BM, true>(l.window) : wgrad_kernel_for<BM, false>(l.window);
+        hipLaunchKernelGGL(k, grid, dim3(kThreads), 0, st, x, dy, dw, g, pps, dbias);
+        return;
+    }
     WgradBatch wbatch;
     wbatch.n = 0;
-    if (batch) wbatch = *batch;              // (only the row-major kernel below reads it; checked by the caller)
-    if (hwc && same && g.Cin == 64) {            // two taps per 128-column tile
-        if (g.R == 3 && g.S == 3)
-            if (g.OW % BK == 0)
-                hipLaunchKernelGGL((conv_wgrad_vec_kernel<BM, 3, 3, true, true>), grid, dim3(kThreads), 0, st, x, dy, dw, g, p_per_split, dbias, wbatch);
-            else
-                hipLaunchKernelGGL((conv_wgrad_vec_kernel<BM, 3, 3, true>), grid, dim3(kThreads), 0, st, x, dy, dw, g, p_per_split, dbias, wbatch);
-        else if (g.R == 1 && g.S == 1)
-            if (g.OW % BK == 0)
-                hipLaunchKernelGGL((conv_wgrad_vec_kernel<BM, 1, 1, true, true>), grid, dim3(kThreads), 0, st, x, dy, dw, g, p_per_split, dbias, wbatch);
-            else
-                hipLaunchKernelGGL((conv_wgrad_vec_kernel<BM, 1, 1, true>), grid, dim3(kThreads), 0, st, x, dy, dw, g, p_per_split, dbias, wbatch);
-        else
-            hipLaunchKernelGGL((conv_wgrad_vec_kernel<BM, 0, 0, true>), grid, dim3(kThreads), 0, st, x, dy, dw, g, p_per_split, dbias, wbatch);
-        return;
+    if (batch) wbatch = *batch;              // (only FI_WGRAD_VEC reads it; checked by the caller)
+    if (l.flags & FI_LAUNCH_SWIZZLED) {      // XCD-aware 1-D launch (see the kernel)
+        g.swz = 1;
+        g.wg_gx = l.grid_x; g.wg_gy = l.grid_y; g.wg_splits = l.grid_z;
+        const long nblk = (long)l.grid_x * l.grid_y * l.grid_z * l.per_launch;
+        grid = dim3((unsigned)(((nblk + 7) / 8) * 8), 1, 1);
     }
-    if (hwc && same) {
-        ConvGeom gs = g;
-        dim3 vgrid = grid;
-        if ((g.P >= 32768 && !getenv("FI_NO_WG_SWZ")) || wbatch.n) {       // XCD-aware 1-D launch (see the kernel)
-            gs.swz = 1;
-            gs.wg_gx = (int)grid.x; gs.wg_gy = (int)grid.y; gs.wg_splits = splits;
-            const long nblk = (long)grid.x * grid.y * splits * (wbatch.n ? wbatch.n : 1);
-            vgrid = dim3((unsigned)(((nblk + 7) / 8) * 8), 1, 1);
-        }
-        if (g.R == 3 && g.S == 3)
-            if (g.OW % BK == 0)
-                hipLaunchKernelGGL((conv_wgrad_vec_kernel<BM, 3, 3, false, true>), vgrid, dim3(kThreads), 0, st, x, dy, dw, gs, p_per_split, dbias, wbatch);
-            else
-                hipLaunchKernelGGL((conv_wgrad_vec_kernel<BM, 3, 3>), vgrid, dim3(kThreads), 0, st, x, dy, dw, gs, p_per_split, dbias, wbatch);
-        else if (g.R == 1 && g.S == 1)
-            if (g.OW % BK == 0)
-                hipLaunchKernelGGL((conv_wgrad_vec_kernel<BM, 1, 1, false, true>), vgrid, dim3(kThreads), 0, st, x, dy, dw, gs, p_per_split, dbias, wbatch);
-            else
-                hipLaunchKernelGGL((conv_wgrad_vec_kernel<BM, 1, 1>), vgrid, dim3(kThreads), 0, st, x, dy, dw, gs, p_per_split, dbias, wbatch);
-        else
-            hipLaunchKernelGGL((conv_wgrad_vec_kernel<BM, 0, 0>), vgrid, dim3(kThreads), 0, st, x, dy, dw, gs, p_per_split, dbias, wbatch);
-        return;
-    }
-    if (hwc) {
-        if (g.R == 3 && g.S == 3)
-            hipLaunchKernelGGL((conv_wgrad_kernel<BM, 3, 3, true>), grid, dim3(kThreads), 0, st, x, dy, dw, g, p_per_split, dbias);
-        else if (g.R == 1 && g.S == 1)
-            hipLaunchKernelGGL((conv_wgrad_kernel<BM, 1, 1, true>), grid, dim3(kThreads), 0, st, x, dy, dw, g, p_per_split, dbias);
-        else
-            hipLaunchKernelGGL((conv_wgrad_kernel<BM, 0, 0, true>), grid, dim3(kThreads), 0, st, x, dy, dw, g, p_per_split, dbias);
-        return;
-    }
-    if (g.R == 3 && g.S == 3)
-        hipLaunchKernelGGL((conv_wgrad_kernel<BM, 3, 3, false>), grid, dim3(kThreads), 0, st, x, dy, dw, g, p_per_split, dbias);
-    else if (g.R == 1 && g.S == 1)
-        hipLaunchKernelGGL((conv_wgrad_kernel<BM, 1, 1, false>), grid, dim3(kThreads), 0, st, x, dy, dw, g, p_per_split, dbias);
-    else if (g.R == 7 && g.S == 7)
-        hipLaunchKernelGGL((conv_wgrad_kernel<BM, 7, 7, false>), grid, dim3(kThreads), 0, st, x, dy, dw, g, p_per_split, dbias);
-    else
-        hipLaunchKernelGGL((conv_wgrad_kernel<BM, 0, 0, false>), grid, dim3(kThreads), 0, st, x, dy, dw, g, p_per_split, dbias);
+    const bool u16 = (l.flags & FI_LAUNCH_ROW_UNIFORM) != 0;
+    auto k = l.form == FI_WGRAD_VEC_TWO_TAP ? wgrad_vec_kernel_for<BM, true>(l.window, u16)
+                                            : wgrad_vec_kernel_for<BM, false>(l.window, u16);
+    hipLaunchKernelGGL(k, grid, dim3(kThreads), 0, st, x, dy, dw, g, pps, dbias, wbatch);
+}
+
+void launch_wgrad(const FiConvLaunch &l, const ConvGeom &g, const float *x, const float *dy, float *dw, float *dbias,
+                  hipStream_t st, const WgradBatch *batch = nullptr)
+{
+    (l.tile_rows == 64 ? launch_wgrad_bm<64> : launch_wgrad_bm<128>)(l, g, x, dy, dw, dbias, st, batch);
 }
 
 // -------------------------------------------------------------------------------------
-// Kernel selection.  A planner validates the arguments and decides which kernel a call runs -- host arithmetic on
-// sizes, layouts and pointer VALUES, no HIP call -- and the entry point launches exactly what the plan says.  The
-// fi_*_plan queries at the end of this file run the same planners, so that whoever keeps books per kernel
-// (conv.FLOP_LOG, bench.py) asks the library instead of restating its rules.
+// Kernel selection.  A planner validates the arguments and decides EVERYTHING about the launches of a call -- kernel
+// form, tiles, flags, grid: a FiConvLaunch (include/fi_capi.h, which states the rules) per launch -- by host arithmetic
+// on sizes, layouts, pointer VALUES and the FI_* switches of the environment, no HIP call; the launchers above and the
+// entry points only dispatch on it.  The fi_*_plan and fi_*_launch(es) queries at the end of this file run the same
+// planners, so that whoever keeps books per kernel (conv.FLOP_LOG, bench.py) or tests a branch asks the library instead
+// of restating its rules.
 // -------------------------------------------------------------------------------------
-enum FwdPath { FWD_GENERIC, FWD_PATCH, FWD_PATCH_FLAT, FWD_REG1X1, FWD_RING };
-
 struct FwdPlan {
-    FwdPath path;
-    bool bm64;        // FWD_GENERIC: 64-row tiles (128 otherwise)
-    bool hwc;         // tap-major weights: the fast gather path
-    bool wino;        // FWD_PATCH / FWD_PATCH_FLAT: the Winograd F(2x2,3x3) form (conv3x3_wino_flat_kernel); same counter
-    int kernel_id;    // FI_K_*: the profiling counter of the launch
+    int n;                 // launches: 1, or 2 for the main / tail pair of the generic kernel (one counter: l[0].kernel_id)
+    FiConvLaunch l[2];
 };
 
-// fi_conv2d_forward_live's arguments (without the live count and the stream) -> g (all but zero / n_live) and the plan
+// fi_conv2d_forward_live's arguments (without the stream; live: a device-side live count is given) -> g (all but zero /
+// n_live and the per-launch fields) and the plan
 int plan_forward(ConvGeom &g, FwdPlan &p, const float *x, const float *weight, const float *residual, const float *gate,
                  const float *y, int N, int Cin, int H, int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h,
-                 int pad_w, int weight_layout, int out_h, int out_w, int output_layout)
+                 int pad_w, int weight_layout, int out_h, int out_w, int output_layout, bool live)
 {
     int rc = make_geom(g, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w, out_h, out_w);
     if (rc != FI_OK) return rc;
@@ -2069,25 +2002,32 @@ int plan_forward(ConvGeom &g, FwdPlan &p, const float *x, const float *weight, c
     FI_REQUIRE(weight_layout >= 0 && weight_layout <= 3,
                "weight_layout: 0 = [Cout][Cin][R][S], 1 = [Cout][R][S][Cin], 2 = 1 with the taps reversed, 3 = fragment-major 1x1");
     // tap-major fast path: channels-last weights (any 1x1 weight is both layouts at once)
-    p.hwc = (Cin % BK == 0) && (R * S <= 64) && (weight_layout >= 1 || R * S == 1);
-    FI_REQUIRE(p.hwc || weight_layout == 0, "weight_layout 1/2/3 needs Cin % 16 == 0 and R*S <= 64");
+    const bool hwc = (Cin % BK == 0) && (R * S <= 64) && (weight_layout >= 1 || R * S == 1);
+    FI_REQUIRE(hwc || weight_layout == 0, "weight_layout 1/2/3 needs Cin % 16 == 0 and R*S <= 64");
     g.flip = (weight_layout == 2) ? 1 : 0;
-    p.wino = false;
-    // generic kernel: 64-row tiles for narrow layers, and for grids that would leave the chip under-filled with
-    // 128-row tiles (fewer than 2 workgroups per CU): C4/C5 of the backbone at batch 4
-    p.bm64 = Cout <= 64 || (long)fi::ceil_div(g.P, BN) * fi::ceil_div(Cout, 128) < 512;
+    const bool aligned16 = (uintptr_t)y % 16 == 0 && (residual == nullptr || (uintptr_t)residual % 16 == 0) &&
+                           (gate == nullptr || (uintptr_t)gate % 16 == 0);
+    const int mtiles = fi::ceil_div(Cout, 128);
+    p.n = 1;
+    FiConvLaunch &l = p.l[0];
+    l = FiConvLaunch{};
+    l.tile_rows = l.tile_pixels = 128;
+    l.window = window_class(R, S);
+    l.flags = (hwc ? FI_LAUNCH_TAP_MAJOR : 0) | (g.out_nhwc ? FI_LAUNCH_CHANNELS_LAST : 0);
+    l.grid_y = l.grid_z = 1;
+    l.pixels = g.P;
     // fragment-major 1x1 weights (weight_layout 3, made by fi_weight_transpose_batch): the persistent ring form of the
     // weights-in-registers kernel below (same counter)
     if (weight_layout == 3) {
         FI_REQUIRE(fi_conv1x1_ring_eligible(N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w, output_layout, x, y,
                                             residual, gate) == 1,
                    "weight_layout 3 (fragment-major 1x1 weights): shape or alignment not eligible for conv1x1_ring_kernel");
-        p.path = FWD_RING;
-        p.kernel_id = FI_K_CONV1X1_REG;
+        l.form = FI_FWD_RING;
+        l.kernel_id = FI_K_CONV1X1_REG;
         return FI_OK;
     }
     // 3x3 / stride 1 / pad 1 layers with enough tiles to fill the chip: input patch in LDS (conv3x3_patch_kernel)
-    int patch = getenv("FI_NO_PATCH") ? 0 : patch_eligible(g, p.hwc, weight_layout, x, y, residual);
+    int patch = getenv("FI_NO_PATCH") ? 0 : patch_eligible(g, hwc, weight_layout, x, y, residual);
     if (patch == 2 && gate != nullptr && (uintptr_t)gate % 8 != 0) patch = 0;
     // 1x1 / stride 1 layers: weights in registers, pixel tile staged 32 channels at a time (conv1x1_reg_kernel);
     // layers with fewer than 128 input channels are bound by their output stream and measured faster on
@@ -2097,54 +2037,114 @@ int plan_forward(ConvGeom &g, FwdPlan &p, const float *x, const float *weight, c
                         (uintptr_t)x % 16 == 0 && (long)N * Cin * H * W < 2147483647L &&
                         (long)fi::ceil_div(N * H * W, 128) * fi::ceil_div(Cout, 128) >= 256;
     if (patch) {
-        p.path = patch == 2 ? FWD_PATCH_FLAT : FWD_PATCH;
-        p.kernel_id = FI_K_CONV3X3_PATCH + (patch - 1);
+        l.kernel_id = FI_K_CONV3X3_PATCH + (patch - 1);
+        l.form = patch == 1 ? FI_FWD_PATCH : (patch_flat_rows(W) <= PT_ROWS_FLAT ? FI_FWD_PATCH_FLAT13 : FI_FWD_PATCH_FLAT14);
+        const int ptiles = patch == 2 ? fi::ceil_div(N * H * W, 128) : fi::ceil_div(N * H, PT_TH) * fi::ceil_div(W, PT_TW);
+        if (W % 4 == 0 && aligned16) l.flags |= FI_LAUNCH_VEC_OUT;
+        const bool wino_ok = Cin % BK == 0 && Cin >= 64 && !getenv("FI_NO_WINOGRAD");
         // 14 x 14 maps (7 x 7 Winograd tiles, none ragged) with at least 4 channel blocks: 2.25x fewer MFMAs.  The
         // launch fills the chip by the flat kernel's own rule (patch == 2); FI_NO_WINOGRAD keeps the direct form.
-        p.wino = patch == 2 && H == fi::WINO_HW && W == fi::WINO_HW && Cin % BK == 0 && Cin >= 64 && !getenv("FI_NO_WINOGRAD");
+        if (patch == 2 && H == fi::WINO_HW && W == fi::WINO_HW && wino_ok) l.form = FI_FWD_WINO14;
         // 2-D maps (patch == 1) with even H: the same kernel with H and W at run time -- NCHW output only, y / residual /
         // gate 8-byte aligned for the float2 accesses of its epilogue (by alignment, never by presence).  Every grid size
         // of the rule is taken: interleaved with the direct kernel (scripts/patch_probe.py, profiles/wino2d_probe.txt,
         // medians of 5 rounds, spread under 1 %) it is 1.45x faster at 256 workgroups (64 x 64, 256 -> 256, N 4), 1.32x
         // at 512 (128 x 128, 128 -> 128), 1.42x at 1024, 1.41x at 2048, 1.36x at 4096 and 1.36x at 8192 (256 x 256,
         // 256 -> 512).  Below the rule's 256 workgroups the layer stays on conv_fwd_kernel.
-        if (patch == 1 && H % 2 == 0 && Cin % BK == 0 && Cin >= 64 && !g.out_nhwc && (uintptr_t)y % 8 == 0 &&
-            (uintptr_t)residual % 8 == 0 && (uintptr_t)gate % 8 == 0 && !getenv("FI_NO_WINOGRAD"))
-            p.wino = true;
+        if (patch == 1 && H % 2 == 0 && wino_ok && !g.out_nhwc && (uintptr_t)y % 8 == 0 && (uintptr_t)residual % 8 == 0 &&
+            (uintptr_t)gate % 8 == 0)
+            l.form = FI_FWD_WINO;
+        const bool wino = l.form == FI_FWD_WINO14 || l.form == FI_FWD_WINO;
+        if (wino) l.flags &= ~FI_LAUNCH_VEC_OUT;
+        // both kernels: an XCD-banded 1-D grid, the pixel tiles (Winograd: groups of WINO_GROUP 2 x 2 tiles) padded to 8
+        l.grid_x = fi::ceil_div(wino ? fi::ceil_div(N * (H / 2) * (W / 2), fi::WINO_GROUP) : ptiles, 8) * 8 * mtiles;
     } else if (reg1x1) {
-        p.path = FWD_REG1X1;
-        p.kernel_id = FI_K_CONV1X1_REG;
+        l.form = FI_FWD_REG1X1;
+        l.kernel_id = FI_K_CONV1X1_REG;
+        if (aligned16) l.flags |= FI_LAUNCH_VEC_OUT;
+        l.grid_x = fi::ceil_div(fi::ceil_div(N * H * W, 128), 8) * 8 * mtiles;
     } else {
-        p.path = FWD_GENERIC;
-        p.kernel_id = FI_K_CONV_FWD + (p.bm64 ? 0 : 4) + window_class(R, S);
+        // generic kernel: 64-row tiles for narrow layers, and for grids that would leave the chip under-filled with
+        // 128-row tiles (fewer than 2 workgroups per CU): C4/C5 of the backbone at batch 4
+        const bool bm64 = Cout <= 64 || (long)fi::ceil_div(g.P, BN) * mtiles < 512;
+        const long slots = 1024;                                  // resident workgroups: 256 CUs x 4
+        const long ny = fi::ceil_div(Cout, bm64 ? 64 : 128), wgs = fi::ceil_div(g.P, BN) * ny, rem = wgs % slots;
+        const bool nchw_tap = hwc && !g.out_nhwc;                 // the only layout with 64-pixel-tile instantiations
+        l.form = FI_FWD_GENERIC;
+        l.kernel_id = FI_K_CONV_FWD + (bm64 ? 0 : 4) + l.window;
+        l.tile_rows = bm64 ? 64 : 128;
+        if (hwc ? l.window == FI_WIN_7X7 : l.window == FI_WIN_1X1) l.window = FI_WIN_OTHER;     // not instantiated
+        if (!g.out_nhwc && (g.OH * g.OW) % 4 == 0 && aligned16) l.flags |= FI_LAUNCH_VEC_OUT;
+        l.grid_y = (int)ny;
+        // 64-pixel tiles when even 64-row tiles leave fewer than 4 workgroups per CU (C4/C5 of the backbone
+        // at batch 4): twice the workgroups, so that 4 wavefronts share each SIMD's MFMA pipe
+        if (bm64 && nchw_tap && wgs < slots && g.P >= 64) {
+            l.tile_pixels = 64;
+            l.grid_x = fi::ceil_div(g.P, 64);
+            return FI_OK;
+        }
+        // Tail launch.  All tiles of a layer cost the same, so a grid of r.f "rounds" of the 1024 resident
+        // workgroups ends with a round that uses a fraction f of the chip (mask head: 6272 tiles = 6.125
+        // rounds).  A small remainder is cut off and run as 64x64 tiles -- 4x the workgroups, a quarter of the
+        // work each -- so that it spreads over all CUs.
+        if (!bm64 && nchw_tap && wgs > slots && rem > 0 && rem * 3 < slots && slots % ny == 0) {
+            FiConvLaunch &t = p.l[p.n++];
+            t = l;
+            l.pixels = (int)((wgs / slots) * (slots / ny)) * BN;
+            t.p_base = l.pixels;
+            t.pixels = g.P - l.pixels;
+            t.tile_rows = t.tile_pixels = 64;
+            t.grid_x = fi::ceil_div(t.pixels, 64);
+            t.grid_y = fi::ceil_div(Cout, 64);
+        }
+        l.grid_x = fi::ceil_div(l.pixels, BN);
+        // XCD-aware order for large compute-bound grids; short-K 1x1 layers are bound by their output
+        // stream and small grids by occupancy -- both measured faster in the plain order
+        // (not with a device-side live count: the live tiles are the FIRST ones, and a band per XCD would hand them all to one
+        // or two XCDs)
+        if (l.grid_x >= 512 && (R * S > 1 || g.K >= 128) && !live) {
+            l.flags |= FI_LAUNCH_SWIZZLED;
+            l.grid_x = fi::ceil_div(l.grid_x, 8) * 8;
+        }
     }
     return FI_OK;
 }
 
-struct WgradPlan {
-    int bm;           // tile rows (output channels): 64 or 128
-    int splits;       // pixel splits (grid.z)
-    int pps;          // pixels per split, a multiple of BK
-    int kernel_id;    // FI_K_*
-};
-
-// Tile and split choice of the weight-gradient kernels for dW [Cout][K] summed over P pixels, nb problems of that
-// geometry in one launch.  min_pix: fewest pixels a split may have; force_bm: 0 or a tile height to take whatever the
-// grid; target_wg: the workgroups tiles x splits should reach (the 1024 resident slots, 256 CUs x 4).
-WgradPlan plan_wgrad(int Cout, int K, int P, int R, int S, int nb, int min_pix, int force_bm, long target_wg)
+// The kernel form (FI_WGRAD_*) of a weight gradient in weight_layout (any 1x1 weight is both layouts at once).  Tap-major dW
+// needs 128 input channels of one tap per column tile, or (Cin == 64, vector kernel only) the 64 channels of two taps; a layer
+// that has neither answers FI_WGRAD_SCALAR_ROW_MAJOR to a tap-major request.  THE predicate behind
+// fi_conv2d_weight_grad_layout, the layout check of the entries and what may share a launch (FI_WGRAD_VEC).
+int wgrad_form(const ConvGeom &g, const float *x, const float *dy, int weight_layout = 1)
 {
-    WgradPlan p;
-    // 64-row tiles for narrow layers, and when 128-row tiles x the admissible splits
-    // would fill less than 3/4 of the resident slots (C4/C5 1x1 layers at batch 4)
+    const bool same = wgrad_same_size(g, x, dy);
+    if (weight_layout != 1 && g.R * g.S != 1) return FI_WGRAD_SCALAR_ROW_MAJOR;
+    if (g.Cin == 64 && same) return FI_WGRAD_VEC_TWO_TAP;
+    if (g.Cin % BN != 0) return FI_WGRAD_SCALAR_ROW_MAJOR;
+    return same ? FI_WGRAD_VEC : FI_WGRAD_SCALAR_TAP_MAJOR;
+}
+
+// The launch of a weight gradient dW [Cout][K] summed over P pixels in kernel form `form`: nb problems of geometry g in one
+// launch (batched: they travel in a WgradBatch, whatever nb).  gemm: fi_gemm_nt's product (Cout = M, Cin = N, pixels = K).
+// min_pix: fewest pixels a split may have; force_bm: 0 or a tile height to take whatever the grid; target_wg: the workgroups
+// tiles x splits should reach (the resident slots, 256 CUs x 4) -- tuning knobs (scripts/), read once, FI_WG_* not for the GEMM
+void plan_wgrad(FiConvLaunch &l, const ConvGeom &g, int form, int nb, bool batched, bool gemm)
+{
+    static const int wg_min_pix = getenv("FI_WG_MINPIX") ? atoi(getenv("FI_WG_MINPIX")) : 512;
+    static const int wg_bm = getenv("FI_WG_BM") ? atoi(getenv("FI_WG_BM")) : 0;
+    static const long gemm_target = getenv("FI_GEMM_TARGET") ? atol(getenv("FI_GEMM_TARGET")) : 1024;
+    const int min_pix = gemm ? 512 : wg_min_pix, force_bm = gemm ? 0 : wg_bm;
+    const long target_wg = gemm ? gemm_target : 1024;
+    const int Cout = g.Cout, K = g.K, P = g.P;
+    // 64-row tiles for narrow layers, and when 128-row tiles x the admissible splits would fill less than 3/4 of the
+    // resident slots (C4/C5 1x1 layers at batch 4)
     const long max_splits = ((long)P + min_pix - 1) / min_pix;
     const long tiles128 = (long)fi::ceil_div(K, BN) * fi::ceil_div(Cout, 128);
     const long per128 = 1024 / tiles128 < 1 ? 1 : 1024 / tiles128;
     const long reach128 = nb * tiles128 * (per128 < max_splits ? per128 : max_splits);
-    p.bm = force_bm ? (Cout <= 64 ? 64 : force_bm) : ((Cout <= 64 || reach128 < 768) ? 64 : 128);
-    const long tiles = (long)fi::ceil_div(K, BN) * fi::ceil_div(Cout, p.bm);
-    // Split the pixel range so that tiles x splits fills the resident workgroup slots
-    // in ONE round: every workgroup has the same amount of work, so 1044 workgroups on 1024 slots take
-    // two rounds (the first version rounded UP and paid exactly that).
+    const int bm = force_bm ? (Cout <= 64 ? 64 : force_bm) : ((Cout <= 64 || reach128 < 768) ? 64 : 128);
+    const long tiles = (long)fi::ceil_div(K, BN) * fi::ceil_div(Cout, bm);
+    // Split the pixel range so that tiles x splits fills the resident workgroup slots in ONE round: every workgroup has
+    // the same amount of work, so 1044 workgroups on 1024 slots take two rounds (the first version rounded UP and paid that).
     // (a batch of nb problems fills the slots together: fewer, longer pixel splits per problem -- the fixed cost of a
     // workgroup, prologue and atomic epilogue, is paid per split)
     const long want = target_wg / (tiles * nb);
@@ -2165,10 +2165,23 @@ WgradPlan plan_wgrad(int Cout, int K, int P, int R, int S, int nb, int min_pix, 
             }
         }
     }
-    p.pps = fi::ceil_div(fi::ceil_div(P, splits), BK) * BK;
-    p.splits = fi::ceil_div(P, p.pps);
-    p.kernel_id = FI_K_CONV_WGRAD + (p.bm == 64 ? 0 : 4) + window_class(R, S);
-    return p;
+    l = FiConvLaunch{};
+    l.form = form;
+    l.tile_rows = bm;
+    l.window = window_class(g.R, g.S);
+    l.kernel_id = FI_K_CONV_WGRAD + (bm == 64 ? 0 : 4) + l.window;
+    if (l.window == FI_WIN_7X7 && form != FI_WGRAD_SCALAR_ROW_MAJOR) l.window = FI_WIN_OTHER;      // not instantiated
+    const bool vec = form == FI_WGRAD_VEC || form == FI_WGRAD_VEC_TWO_TAP;
+    if (form != FI_WGRAD_SCALAR_ROW_MAJOR) l.flags |= FI_LAUNCH_TAP_MAJOR;
+    if (vec && g.OW % BK == 0 && l.window != FI_WIN_OTHER) l.flags |= FI_LAUNCH_ROW_UNIFORM;
+    if (form == FI_WGRAD_VEC && ((P >= 32768 && !getenv("FI_NO_WG_SWZ")) || batched)) l.flags |= FI_LAUNCH_SWIZZLED;
+    l.pixels = P;
+    l.pixels_per_split = fi::ceil_div(fi::ceil_div(P, splits), BK) * BK;
+    l.splits = fi::ceil_div(P, l.pixels_per_split);
+    l.per_launch = nb;
+    l.grid_x = fi::ceil_div(K, BN);
+    l.grid_y = fi::ceil_div(Cout, bm);
+    l.grid_z = l.splits;
 }
 
 // -------------------------------------------------------------------------------------
@@ -2457,71 +2470,56 @@ int fi_conv2d_forward_live(const float *x, const float *weight, const float *bia
                            int weight_layout, int out_h, int out_w, int output_layout, const int32_t *n_live_dev,
                            fi_stream_t stream)
 {
+#ifdef FI_PROBE_1X1
+    if (getenv("FI_DBG_1X1")) relu |= (int)strtol(getenv("FI_DBG_1X1"), nullptr, 0);
+#endif
     ConvGeom g;
     FwdPlan plan;
     const int rc = plan_forward(g, plan, x, weight, residual, gate, y, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h,
-                                pad_w, weight_layout, out_h, out_w, output_layout);
+                                pad_w, weight_layout, out_h, out_w, output_layout, n_live_dev != nullptr);
     if (rc != FI_OK) return rc;
     g.zero = zero_page();
     FI_REQUIRE(g.zero != nullptr, "zero page lookup failed (no HIP device?)");
     g.n_live = n_live_dev;        // honoured by conv_fwd_kernel (every instantiation); the patch / 1x1 kernels compute all
     hipStream_t st = (hipStream_t)stream;
-#ifdef FI_PROBE_1X1
-    if (getenv("FI_DBG_1X1")) relu |= (int)strtol(getenv("FI_DBG_1X1"), nullptr, 0);
-#endif
     const Epilogue ep = {bias, scale, residual, relu, gate};
-    fi::ProfScope prof(plan.kernel_id, st);
-    if (plan.path == FWD_RING) {
+    const FiConvLaunch &l = plan.l[0];
+    const int vec4 = (l.flags & FI_LAUNCH_VEC_OUT) ? 1 : 0;
+    const dim3 grid1d((unsigned)l.grid_x);
+    fi::ProfScope prof(l.kernel_id, st);
+    switch (l.form) {
+    case FI_FWD_RING: {
         const fi::RingArgs ra = {x, weight, bias, scale, residual, gate, y, g.zero, N, Cin, H * W, Cout, relu & 1};
         fi::launch_conv1x1_ring(ra, st);
-        FI_HIP_CHECK(hipGetLastError());
-        return FI_OK;
+        break;
     }
-    if (plan.path == FWD_REG1X1) {
-        Conv1x1Geom cg;
-        cg.N = N; cg.Cin = Cin; cg.HW = H * W; cg.Cout = Cout;
-        cg.ptiles = fi::ceil_div(N * H * W, 128);
-        cg.mtiles = fi::ceil_div(Cout, 128);
-        cg.vec4 = ((uintptr_t)y % 16 == 0 && (residual == nullptr || (uintptr_t)residual % 16 == 0) &&
-                   (gate == nullptr || (uintptr_t)gate % 16 == 0)) ? 1 : 0;
-        cg.zero = g.zero;
-        const long blocks = (long)fi::ceil_div(cg.ptiles, 8) * 8 * cg.mtiles;
-        hipLaunchKernelGGL(conv1x1_reg_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, x, weight, ep, y, cg);
-        FI_HIP_CHECK(hipGetLastError());
-        return FI_OK;
+    case FI_FWD_REG1X1: {
+        const Conv1x1Geom cg = {N, Cin, H * W, Cout, fi::ceil_div(N * H * W, 128), fi::ceil_div(Cout, 128), vec4, g.zero};
+        hipLaunchKernelGGL(conv1x1_reg_kernel, grid1d, dim3(kThreads), 0, st, x, weight, ep, y, cg);
+        break;
     }
-    if ((plan.path == FWD_PATCH || plan.path == FWD_PATCH_FLAT) && plan.wino) {
-        const fi::WinoArgs wa = {x, weight, bias, scale, residual, gate, y, g.zero, N, Cin, H, W, Cout, relu, g.flip};
+    case FI_FWD_WINO14:
+    case FI_FWD_WINO: {
+        const fi::WinoArgs wa = {x, weight, bias, scale, residual, gate, y, g.zero, N, Cin, H, W, Cout, relu, g.flip,
+                                 l.form == FI_FWD_WINO14, l.grid_x};
         fi::launch_conv3x3_wino_flat(wa, st);
-        FI_HIP_CHECK(hipGetLastError());
-        return FI_OK;
+        break;
     }
-    if (plan.path == FWD_PATCH || plan.path == FWD_PATCH_FLAT) {
-        const bool flat = plan.path == FWD_PATCH_FLAT;
-        PatchGeom pg;
-        pg.N = N; pg.Cin = Cin; pg.H = H; pg.W = W; pg.Cout = Cout;
-        pg.flip = g.flip;
-        pg.tiles_x = fi::ceil_div(W, PT_TW);
-        pg.ptiles = flat ? fi::ceil_div(N * H * W, 128) : fi::ceil_div(N * H, PT_TH) * pg.tiles_x;
-        pg.mtiles = fi::ceil_div(Cout, 128);
-        pg.vec4 = (W % 4 == 0 && (uintptr_t)y % 16 == 0 && (residual == nullptr || (uintptr_t)residual % 16 == 0) &&
-                   (gate == nullptr || (uintptr_t)gate % 16 == 0)) ? 1 : 0;
-        pg.out_nhwc = g.out_nhwc;
-        pg.zero = g.zero;
-        const long blocks = (long)fi::ceil_div(pg.ptiles, 8) * 8 * pg.mtiles;
-        if (flat && patch_flat_rows(W) <= PT_ROWS_FLAT)
-            hipLaunchKernelGGL(conv3x3_patch_kernel<true>, dim3((unsigned)blocks), dim3(kThreads), 0, st, x, weight, ep, y, pg);
-        else if (flat)
-            hipLaunchKernelGGL((conv3x3_patch_kernel<true, PT_ROWS_FLAT_MAX>), dim3((unsigned)blocks), dim3(kThreads), 0, st, x, weight, ep, y, pg);
-        else
-            hipLaunchKernelGGL(conv3x3_patch_kernel<false>, dim3((unsigned)blocks), dim3(kThreads), 0, st, x, weight, ep, y, pg);
-        FI_HIP_CHECK(hipGetLastError());
-        return FI_OK;
+    case FI_FWD_PATCH:
+    case FI_FWD_PATCH_FLAT13:
+    case FI_FWD_PATCH_FLAT14: {
+        const int tiles_x = fi::ceil_div(W, PT_TW);
+        const int ptiles = l.form == FI_FWD_PATCH ? fi::ceil_div(N * H, PT_TH) * tiles_x : fi::ceil_div(N * H * W, 128);
+        const PatchGeom pg = {N, Cin, H, W, Cout, g.flip, tiles_x, ptiles, fi::ceil_div(Cout, 128), vec4, g.out_nhwc, g.zero};
+        auto k = l.form == FI_FWD_PATCH ? conv3x3_patch_kernel<false>
+                                        : (l.form == FI_FWD_PATCH_FLAT13 ? conv3x3_patch_kernel<true>
+                                                                         : conv3x3_patch_kernel<true, PT_ROWS_FLAT_MAX>);
+        hipLaunchKernelGGL(k, grid1d, dim3(kThreads), 0, st, x, weight, ep, y, pg);
+        break;
     }
-    if (plan.bm64)
-        launch_fwd<64>(g, x, weight, ep, y, plan.hwc, st);
-    else
-        launch_fwd<128>(g, x, weight, ep, y, plan.hwc, st);
+    default:
+        for (int i = 0; i < plan.n; ++i) launch_fwd(plan.l[i], g, x, weight, ep, y, st);
+    }
     FI_HIP_CHECK(hipGetLastError());
     return FI_OK;
 }
@@ -2532,12 +2530,28 @@ int fi_conv2d_forward_plan(const float *x, const float *weight, const float *bia
                            int weight_layout, int out_h, int out_w, int output_layout, int *kernel_id)
 {
     FI_REQUIRE(kernel_id != nullptr, "null pointer");
+    FiConvLaunch l[2];
+    int n;
+    const int rc = fi_conv2d_forward_launches(x, weight, bias, scale, residual, gate, y, N, Cin, H, W, Cout, R, S, stride_h,
+                                              stride_w, pad_h, pad_w, relu, weight_layout, out_h, out_w, output_layout, l, &n);
+    if (rc == FI_OK) *kernel_id = l[0].kernel_id;
+    return rc;
+}
+
+int fi_conv2d_forward_launches(const float *x, const float *weight, const float *bias, const float *scale,
+                               const float *residual, const float *gate, float *y, int N, int Cin, int H, int W,
+                               int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int relu,
+                               int weight_layout, int out_h, int out_w, int output_layout, FiConvLaunch *out, int *n)
+{
+    FI_REQUIRE(out != nullptr && n != nullptr, "null pointer");
     ConvGeom g;
     FwdPlan plan;
     const int rc = plan_forward(g, plan, x, weight, residual, gate, y, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h,
-                                pad_w, weight_layout, out_h, out_w, output_layout);
-    if (rc == FI_OK) *kernel_id = plan.kernel_id;
-    return rc;
+                                pad_w, weight_layout, out_h, out_w, output_layout, false);
+    if (rc != FI_OK) return rc;
+    *n = plan.n;
+    for (int i = 0; i < plan.n; ++i) out[i] = plan.l[i];
+    return FI_OK;
 }
 
 int fi_bn_act_backward(const float *dy, const float *y, const float *scale, const float *gamma,
@@ -2589,40 +2603,18 @@ int fi_bn_act_backward(const float *dy, const float *y, const float *scale, cons
     return FI_OK;
 }
 
-// 1: this geometry runs on conv_wgrad_vec_kernel's plain (non-HALF) instantiation -- the one that takes a WgradBatch
-static bool wgrad_batchable(const ConvGeom &g, const float *x, const float *dy, int weight_layout)
-{
-    const bool hwc = (g.Cin % BN == 0) && (weight_layout == 1 || g.R * g.S == 1);
-    return hwc && wgrad_same_size(g, x, dy);
-}
-
-// tap-major dW: 128 input channels of one tap per column tile, or (Cin == 64, row-major kernel only) the 64 channels
-// of two taps
-static bool wgrad_tap_major_ok(const ConvGeom &g, const float *x, const float *dy)
-{
-    return g.Cin % BN == 0 || (g.Cin == 64 && wgrad_same_size(g, x, dy));
-}
-
-// fi_conv2d_weight_grad's argument checks -> g (all but zero) and hwc
-static int wgrad_checked(ConvGeom &g, bool &hwc, const float *x, const float *dy, const float *dweight, int N, int Cin, int H,
+// fi_conv2d_weight_grad's argument checks -> g (all but zero) and the kernel form (FI_WGRAD_*) of the call
+static int wgrad_checked(ConvGeom &g, int &form, const float *x, const float *dy, const float *dweight, int N, int Cin, int H,
                          int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int weight_layout)
 {
     int rc = make_geom(g, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w);
     if (rc != FI_OK) return rc;
     FI_REQUIRE(x && dy && dweight, "null pointer");
     FI_REQUIRE(weight_layout == 0 || weight_layout == 1, "weight_layout: 0 = [Cout][Cin][R][S], 1 = [Cout][R][S][Cin]");
-    hwc = wgrad_tap_major_ok(g, x, dy) && (weight_layout == 1 || R * S == 1);
-    FI_REQUIRE(hwc || weight_layout == 0,
+    form = wgrad_form(g, x, dy, weight_layout);
+    FI_REQUIRE(form != FI_WGRAD_SCALAR_ROW_MAJOR || weight_layout == 0,
                "weight_layout 1 needs Cin % 128 == 0, or Cin == 64 on a same-size stride-1 layer");
     return FI_OK;
-}
-
-// the plan of a launch that carries nb problems of geometry g
-static WgradPlan wgrad_conv_plan(const ConvGeom &g, int nb)
-{
-    static const int min_pix = getenv("FI_WG_MINPIX") ? atoi(getenv("FI_WG_MINPIX")) : 512;      // tuning knobs (scripts/)
-    static const int force_bm = getenv("FI_WG_BM") ? atoi(getenv("FI_WG_BM")) : 0;
-    return plan_wgrad(g.Cout, g.K, g.P, g.R, g.S, nb, min_pix, force_bm, 1024);
 }
 
 // how many of n same-geometry problems fi_conv2d_weight_grad_batch puts into its first launch (1: it loops over them)
@@ -2636,7 +2628,27 @@ static int wgrad_batch_size(bool batchable, int n, int flags, bool uniform_db)
 
 static int wgrad_impl(const float *x, const float *dy, float *dweight, int N, int Cin, int H,
                       int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h,
-                      int pad_w, int weight_layout, float *dbias, int flags, fi_stream_t stream, const WgradBatch *batch);
+                      int pad_w, int weight_layout, float *dbias, int flags, fi_stream_t stream, const WgradBatch *batch)
+{
+    ConvGeom g;
+    int form;
+    const int rc = wgrad_checked(g, form, x, dy, dweight, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w,
+                                 weight_layout);
+    if (rc != FI_OK) return rc;
+    FiConvLaunch plan;
+    plan_wgrad(plan, g, form, batch ? batch->n : 1, batch != nullptr, false);
+    g.zero = zero_page();
+    FI_REQUIRE(g.zero != nullptr, "zero page lookup failed (no HIP device?)");
+    hipStream_t st = (hipStream_t)stream;
+    if (!(flags & FI_OUTPUTS_ZEROED)) {
+        FI_HIP_CHECK(hipMemsetAsync(dweight, 0, sizeof(float) * (size_t)Cout * g.K, st));
+        if (dbias) FI_HIP_CHECK(hipMemsetAsync(dbias, 0, sizeof(float) * (size_t)Cout, st));
+    }
+    fi::ProfScope prof(plan.kernel_id, st);
+    launch_wgrad(plan, g, x, dy, dweight, dbias, st, batch);
+    FI_HIP_CHECK(hipGetLastError());
+    return FI_OK;
+}
 
 int fi_conv2d_weight_grad(const float *x, const float *dy, float *dweight, int N, int Cin, int H,
                           int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h,
@@ -2658,7 +2670,7 @@ int fi_conv2d_weight_grad_batch(const float *const *x, const float *const *dy, f
     bool ok = true, any_db = false, all_db = true;
     for (int i = 0; i < n; ++i) {
         FI_REQUIRE(x[i] && dy[i] && dweight[i], "null pointer in the batch");
-        ok = ok && wgrad_batchable(g, x[i], dy[i], weight_layout);
+        ok = ok && wgrad_form(g, x[i], dy[i], weight_layout) == FI_WGRAD_VEC;      // the one form that takes a WgradBatch
         const bool has = dbias && dbias[i];
         any_db = any_db || has;
         all_db = all_db && has;
@@ -2685,29 +2697,19 @@ int fi_conv2d_weight_grad_batch(const float *const *x, const float *const *dy, f
     return FI_OK;
 }
 
-static int wgrad_impl(const float *x, const float *dy, float *dweight, int N, int Cin, int H,
-                      int W, int Cout, int R, int S, int stride_h, int stride_w, int pad_h,
-                      int pad_w, int weight_layout, float *dbias, int flags, fi_stream_t stream, const WgradBatch *batch)
+int fi_conv2d_weight_grad_launch(const float *x, const float *dy, float *dweight, int N, int Cin, int H, int W, int Cout,
+                                 int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int weight_layout,
+                                 float *dbias, int flags, int n, FiConvLaunch *out)
 {
+    FI_REQUIRE(out != nullptr, "null pointer");
+    FI_REQUIRE(n >= 1, "empty batch / null pointer table");
     ConvGeom g;
-    bool hwc;
-    const int rc = wgrad_checked(g, hwc, x, dy, dweight, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w,
+    int form;
+    const int rc = wgrad_checked(g, form, x, dy, dweight, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w,
                                  weight_layout);
     if (rc != FI_OK) return rc;
-    const WgradPlan plan = wgrad_conv_plan(g, batch ? batch->n : 1);
-    g.zero = zero_page();
-    FI_REQUIRE(g.zero != nullptr, "zero page lookup failed (no HIP device?)");
-    hipStream_t st = (hipStream_t)stream;
-    if (!(flags & FI_OUTPUTS_ZEROED)) {
-        FI_HIP_CHECK(hipMemsetAsync(dweight, 0, sizeof(float) * (size_t)Cout * g.K, st));
-        if (dbias) FI_HIP_CHECK(hipMemsetAsync(dbias, 0, sizeof(float) * (size_t)Cout, st));
-    }
-    fi::ProfScope prof(plan.kernel_id, st);
-    if (plan.bm == 64)
-        launch_wgrad<64>(g, x, dy, dweight, plan.splits, plan.pps, hwc, dbias, st, batch);
-    else
-        launch_wgrad<128>(g, x, dy, dweight, plan.splits, plan.pps, hwc, dbias, st, batch);
-    FI_HIP_CHECK(hipGetLastError());
+    const int nb = wgrad_batch_size(form == FI_WGRAD_VEC, n, flags, true);
+    plan_wgrad(*out, g, form, nb, nb > 1, false);
     return FI_OK;
 }
 
@@ -2716,15 +2718,12 @@ int fi_conv2d_weight_grad_plan(const float *x, const float *dy, float *dweight, 
                                float *dbias, int flags, int n, int *kernel_id, int *per_launch)
 {
     FI_REQUIRE(kernel_id != nullptr, "null pointer");
-    FI_REQUIRE(n >= 1, "empty batch / null pointer table");
-    ConvGeom g;
-    bool hwc;
-    const int rc = wgrad_checked(g, hwc, x, dy, dweight, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w,
-                                 weight_layout);
+    FiConvLaunch l;
+    const int rc = fi_conv2d_weight_grad_launch(x, dy, dweight, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w,
+                                                weight_layout, dbias, flags, n, &l);
     if (rc != FI_OK) return rc;
-    const int nb = wgrad_batch_size(wgrad_batchable(g, x, dy, weight_layout), n, flags, true);
-    *kernel_id = wgrad_conv_plan(g, nb).kernel_id;
-    if (per_launch) *per_launch = nb;
+    *kernel_id = l.kernel_id;
+    if (per_launch) *per_launch = l.per_launch;
     return FI_OK;
 }
 
@@ -2734,15 +2733,12 @@ int fi_conv2d_weight_grad_split_plan(const float *x, const float *dy, float *dwe
                                      int *pixels_per_split)
 {
     FI_REQUIRE(splits != nullptr && pixels_per_split != nullptr, "null pointer");
-    FI_REQUIRE(n >= 1, "empty batch / null pointer table");
-    ConvGeom g;
-    bool hwc;
-    const int rc = wgrad_checked(g, hwc, x, dy, dweight, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w,
-                                 weight_layout);
+    FiConvLaunch l;
+    const int rc = fi_conv2d_weight_grad_launch(x, dy, dweight, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w,
+                                                weight_layout, dbias, flags, n, &l);
     if (rc != FI_OK) return rc;
-    const WgradPlan plan = wgrad_conv_plan(g, wgrad_batch_size(wgrad_batchable(g, x, dy, weight_layout), n, flags, true));
-    *splits = plan.splits;
-    *pixels_per_split = plan.pps;
+    *splits = l.splits;
+    *pixels_per_split = l.pixels_per_split;
     return FI_OK;
 }
 
@@ -2753,7 +2749,7 @@ int fi_conv2d_weight_grad_layout(const float *x, const float *dy, int N, int Cin
     ConvGeom g;
     const int rc = make_geom(g, N, Cin, H, W, Cout, R, S, stride_h, stride_w, pad_h, pad_w);
     if (rc != FI_OK) return rc;
-    *weight_layout = wgrad_tap_major_ok(g, x, dy) ? 1 : 0;
+    *weight_layout = wgrad_form(g, x, dy) != FI_WGRAD_SCALAR_ROW_MAJOR ? 1 : 0;
     return FI_OK;
 }
 
@@ -2792,13 +2788,6 @@ __global__ __launch_bounds__(256) void gemm_slab_reduce_kernel(const float *__re
     }
 }
 
-// fi_gemm_nt's tiles and K split: the weight gradient's with Cout = M, Cin = N, pixels = K, one problem, no FI_WG_* knobs
-static WgradPlan gemm_nt_plan(int M, int N, int K)
-{
-    static const long target_wg = getenv("FI_GEMM_TARGET") ? atol(getenv("FI_GEMM_TARGET")) : 1024;      // (tuning knob)
-    return plan_wgrad(M, N, K, 1, 1, 1, 512, 0, target_wg);
-}
-
 // fi_gemm_nt_affine's argument checks -> g (all but zero, dw_slab, n_live)
 static int gemm_nt_checked(ConvGeom &g, const float *a, const float *b, const float *scale, const float *bias, const float *c,
                            int M, int N, int K, const float *workspace)
@@ -2818,8 +2807,11 @@ static int gemm_nt_checked(ConvGeom &g, const float *a, const float *b, const fl
 
 size_t fi_gemm_nt_workspace_bytes(int M, int N, int K)
 {
-    if (M < 1 || N < 1 || K < 1) return 0;
-    return sizeof(float) * (size_t)gemm_nt_plan(M, N, K).splits * (size_t)M * (size_t)N;
+    ConvGeom g;
+    if (M < 1 || N < 1 || K < 1 || make_geom(g, 1, N, 1, K, M, 1, 1, 1, 1, 0, 0) != FI_OK) return 0;
+    FiConvLaunch plan;
+    plan_wgrad(plan, g, FI_WGRAD_VEC, 1, false, true);
+    return sizeof(float) * (size_t)plan.splits * (size_t)M * (size_t)N;
 }
 
 int fi_gemm_nt(const float *a, const float *b, const float *bias, float *c, int M, int N, int K, int relu,
@@ -2842,23 +2834,21 @@ int fi_gemm_nt_affine(const float *a, const float *b, const float *scale, const 
     if (rc != FI_OK) return rc;
     g.zero = zero_page();
     FI_REQUIRE(g.zero != nullptr, "zero page lookup failed (no HIP device?)");
-    const WgradPlan plan = gemm_nt_plan(M, N, K);
+    FiConvLaunch plan;
+    plan_wgrad(plan, g, FI_WGRAD_VEC, 1, false, true);
     g.dw_slab = (long)M * N;
     g.n_live = m_live_dev;
     hipStream_t st = (hipStream_t)stream;
     {
         fi::ProfScope prof(plan.kernel_id, st);
-        if (plan.bm == 64)
-            launch_wgrad<64>(g, b, a, workspace, plan.splits, plan.pps, true, nullptr, st);
-        else
-            launch_wgrad<128>(g, b, a, workspace, plan.splits, plan.pps, true, nullptr, st);
+        launch_wgrad(plan, g, b, a, workspace, nullptr, st);
         FI_HIP_CHECK(hipGetLastError());
     }
     const long total4 = (long)M * N / 4;
     const long blocks = (total4 + 255) / 256;
     fi::ProfScope prof2(FI_K_GEMM_REDUCE, st);
     hipLaunchKernelGGL(gemm_slab_reduce_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, st, workspace,
-                       plan.splits, g.dw_slab, bias, N, relu, c, total4, m_live_dev, plan.bm, scale);
+                       plan.splits, g.dw_slab, bias, N, relu, c, total4, m_live_dev, plan.tile_rows, scale);
     FI_HIP_CHECK(hipGetLastError());
     return FI_OK;
 }
@@ -2867,9 +2857,19 @@ int fi_gemm_nt_plan(const float *a, const float *b, const float *scale, const fl
                     int relu, float *workspace, int *kernel_id)
 {
     FI_REQUIRE(kernel_id != nullptr, "null pointer");
+    FiConvLaunch l;
+    const int rc = fi_gemm_nt_launch(a, b, scale, bias, c, M, N, K, relu, workspace, &l);
+    if (rc == FI_OK) *kernel_id = l.kernel_id;
+    return rc;
+}
+
+int fi_gemm_nt_launch(const float *a, const float *b, const float *scale, const float *bias, float *c, int M, int N, int K,
+                      int relu, float *workspace, FiConvLaunch *out)
+{
+    FI_REQUIRE(out != nullptr, "null pointer");
     ConvGeom g;
     const int rc = gemm_nt_checked(g, a, b, scale, bias, c, M, N, K, workspace);
-    if (rc == FI_OK) *kernel_id = gemm_nt_plan(M, N, K).kernel_id;
+    if (rc == FI_OK) plan_wgrad(*out, g, FI_WGRAD_VEC, 1, false, true);
     return rc;
 }
 

@@ -476,6 +476,95 @@ int fi_gemm_nt_affine(const float *a, const float *b, const float *scale, const 
 int fi_gemm_nt_plan(const float *a, const float *b, const float *scale, const float *bias, float *c, int M, int N, int K,
                     int relu, float *workspace, int *kernel_id);
 
+/* One launch of the fp32 convolution kernels (csrc/conv_igemm.hip, conv3x3_wino.hip) as its planner decided it: everything
+ * the launcher needs besides the operands.  The launchers only dispatch on these fields, and the fi_*_plan queries above
+ * read them.
+ *
+ * Forward forms (fi_conv2d_forward_live; the first rule that applies, in this order):
+ *   FI_FWD_RING        weight_layout 3 (fragment-major 1x1 weights): conv1x1_ring_kernel, which sizes its own persistent
+ *                      grid (grid_x 0 here); the call is rejected where fi_conv1x1_ring_eligible says no
+ *   FI_FWD_PATCH       3x3 / stride 1 / pad 1, same-size output, tap-major weights, Cout > 64, W % 16 == 0, at least 256
+ *                      tiles of 8 x 16 pixels x 128 channels: conv3x3_patch_kernel<false>
+ *   FI_FWD_PATCH_FLAT13 / _FLAT14   ... W in {12, 14}, x / y / residual / gate 8-byte aligned, at least 512 tiles of 128
+ *                      consecutive pixels x 128 channels: conv3x3_patch_kernel<true> staging 13 patch rows (W 14) or 14 (W 12)
+ *   FI_FWD_WINO14      a FLAT slot with H == W == 14, Cin >= 64: conv3x3_wino_flat_kernel<14>
+ *   FI_FWD_WINO        a PATCH slot with even H, Cin >= 64, NCHW output, y / residual / gate 8-byte aligned:
+ *                      conv3x3_wino_flat_kernel<0> (H and W at run time)
+ *   FI_FWD_REG1X1      1x1 / stride 1 / pad 0, NCHW output, Cin % 32 == 0, Cin >= 128, Cout > 64, H * W % 4 == 0, x 16-byte
+ *                      aligned, at least 256 tiles of 128 pixels x 128 channels: conv1x1_reg_kernel
+ *   FI_FWD_GENERIC     everything else: conv_fwd_kernel<tile_rows, window, tap-major, channels-last, tile_pixels>
+ * (FI_NO_PATCH, FI_NO_REG1X1, FI_NO_WINOGRAD in the environment, read per call, switch the patch, register and Winograd forms
+ * off.)  The generic form alone has further choices:
+ *   tile_rows    64 for Cout <= 64 or fewer than 512 tiles of 128 pixels x 128 channels, else 128
+ *   tile_pixels  64 on 64-row tiles of a tap-major NCHW launch with fewer than 1024 workgroups and at least 64 pixels, else 128
+ *   main / tail  a tap-major NCHW launch of T > 1024 tiles of 128 x 128 with 0 < 3 (T mod 1024) < 1024 and a tile-row count
+ *                that divides 1024 is two launches: the whole rounds of 1024 tiles (pixels [0, pixels)), then the rest at
+ *                p_base on 64 x 64 tiles
+ *   SWIZZLED     at least 512 pixel tiles, and 3x3-or-larger window or Cin * R * S >= 128, and no device-side live count:
+ *                XCD-aware tile order, grid_x rounded up to a multiple of 8 (the query plans without a live count)
+ *   VEC_OUT      NCHW output with OH * OW % 4 == 0 and y / residual / gate 16-byte aligned (the patch and register forms
+ *                report their own vector epilogue here: W % 4 == 0 resp. nothing, and the same alignment)
+ *   window       the window the kernel is instantiated for: 7x7 only with row-major weights, 1x1 only with tap-major ones
+ *
+ * Weight-gradient forms (fi_conv2d_weight_grad, _batch, and the product of fi_gemm_nt):
+ *   FI_WGRAD_VEC               tap-major dW, Cin % 128 == 0, on a same-size stride-1 layer with H * W % 4 == 0, W >= 4, x / dy
+ *                              16-byte aligned and under 2 GB: conv_wgrad_vec_kernel<tile_rows, window>
+ *   FI_WGRAD_VEC_TWO_TAP       the same layer with Cin == 64: two taps per 128-column tile
+ *   FI_WGRAD_SCALAR_TAP_MAJOR  tap-major dW, Cin % 128 == 0, any other layer: conv_wgrad_kernel<tile_rows, window, true>
+ *   FI_WGRAD_SCALAR_ROW_MAJOR  dW [Cout][Cin][R][S]: conv_wgrad_kernel<tile_rows, window, false>
+ *   ROW_UNIFORM  vector forms with OW % 16 == 0 on a 1x1 or 3x3 window
+ *   SWIZZLED     FI_WGRAD_VEC with at least 32768 pixels (unless FI_NO_WG_SWZ is set) or with a batch: a 1-D grid of
+ *                grid_x * grid_y * grid_z * per_launch workgroups rounded up to a multiple of 8; grid_x/y/z stay the logical
+ *                grid (column tiles, Cout tiles, pixel splits)
+ *   tile_rows, splits, pixels_per_split   see fi_conv2d_weight_grad_split_plan; per_launch see fi_conv2d_weight_grad_plan */
+enum {
+    FI_FWD_GENERIC = 0,
+    FI_FWD_PATCH = 1,
+    FI_FWD_PATCH_FLAT13 = 2,
+    FI_FWD_PATCH_FLAT14 = 3,
+    FI_FWD_WINO14 = 4,
+    FI_FWD_WINO = 5,
+    FI_FWD_REG1X1 = 6,
+    FI_FWD_RING = 7
+};
+enum {
+    FI_WGRAD_VEC = 0,
+    FI_WGRAD_VEC_TWO_TAP = 1,
+    FI_WGRAD_SCALAR_TAP_MAJOR = 2,
+    FI_WGRAD_SCALAR_ROW_MAJOR = 3
+};
+enum { FI_WIN_1X1 = 0, FI_WIN_3X3 = 1, FI_WIN_7X7 = 2, FI_WIN_OTHER = 3 };      /* run-time R x S */
+enum {
+    FI_LAUNCH_TAP_MAJOR = 1,         /* forward: weights [Cout][R][S][Cin]; weight gradient: dW in that layout */
+    FI_LAUNCH_CHANNELS_LAST = 2,     /* forward: y is [N][OH][OW][Cout] */
+    FI_LAUNCH_VEC_OUT = 4,
+    FI_LAUNCH_SWIZZLED = 8,
+    FI_LAUNCH_ROW_UNIFORM = 16
+};
+typedef struct {
+    int32_t form;                    /* FI_FWD_* / FI_WGRAD_* */
+    int32_t kernel_id;               /* FI_K_*: the profiling counter */
+    int32_t tile_rows, tile_pixels;  /* output channels x pixels of a workgroup's tile (weight gradient: tile_pixels 0) */
+    int32_t window;                  /* FI_WIN_* */
+    int32_t flags;                   /* FI_LAUNCH_* */
+    int32_t grid_x, grid_y, grid_z;
+    int32_t p_base, pixels;          /* forward: the launch computes output pixels [p_base, p_base + pixels) */
+    int32_t splits, pixels_per_split, per_launch;      /* weight gradient */
+} FiConvLaunch;
+/* The launches fi_conv2d_forward_live makes for these arguments (no live count): *n of them, 1 or 2, in out[0 .. *n).
+ * Host-only like fi_conv2d_forward_plan: same checks, same status, nothing dereferenced, nothing launched. */
+int fi_conv2d_forward_launches(const float *x, const float *weight, const float *bias, const float *scale,
+                               const float *residual, const float *gate, float *y, int N, int Cin, int H, int W,
+                               int Cout, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int relu,
+                               int weight_layout, int out_h, int out_w, int output_layout, FiConvLaunch *out, int *n);
+/* ... the launch of fi_conv2d_weight_grad / the first launch of fi_conv2d_weight_grad_batch (arguments as for
+ * fi_conv2d_weight_grad_plan), and the product launch of fi_gemm_nt / _rows / _affine. */
+int fi_conv2d_weight_grad_launch(const float *x, const float *dy, float *dweight, int N, int Cin, int H, int W, int Cout,
+                                 int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int weight_layout,
+                                 float *dbias, int flags, int n, FiConvLaunch *out);
+int fi_gemm_nt_launch(const float *a, const float *b, const float *scale, const float *bias, float *c, int M, int N, int K,
+                      int relu, float *workspace, FiConvLaunch *out);
+
 /* All layers' W^T for the data-gradient kernel in one launch: for every descriptor, src is
  * [rows][taps][cols] (a weight stored [Cout][R][S][Cin]) and dst becomes [cols][taps][rows]
  * ([Cin][R][S][Cout]).  tile_base = number of 32x32 tiles of all earlier descriptors

@@ -54,7 +54,7 @@ class Wrapped(object):
 
     def __getattr__(self, name):
         fn = getattr(self._real, name)
-        if not name.startswith("fi_conv") or name.endswith("_eligible") or "_plan" in name or name.endswith("_layout"):
+        if not name.startswith("fi_conv") or name.endswith("_eligible") or "_plan" in name or "_launch" in name or name.endswith("_layout"):
             return fn                                             # (host-side queries, not launches)
         # the 16-bit entries plan their kernel: label the launch by the variant their own query names
         query = getattr(self._real, name.replace("_live_", "_plan_")) if name.startswith("fi_conv2d_forward_live_") else None

@@ -246,6 +246,143 @@ def test_plan_queries_name_the_kernel_on_both_sides_of_every_threshold():
         assert _planned(L.fi_gemm_nt_plan, *g) == L.fi_gemm_nt_affine(*g, None, None) == -1, g
 
 
+def _with_env(name, fn):
+    """fn() with `name`=1 in the environment (the library reads these switches per call)."""
+    assert name not in os.environ
+    os.environ[name] = "1"
+    try:
+        return fn()
+    finally:
+        del os.environ[name]
+
+
+def test_launch_queries_hold_every_decision_of_a_launch_on_both_sides_of_its_threshold():
+    """fi_conv2d_forward_launches / fi_conv2d_weight_grad_launch / fi_gemm_nt_launch answer with the whole launch plan --
+    form, tiles, flags, grid, the pixel ranges of a main / tail pair -- that the launchers dispatch on.  Aligned fake
+    pointers; the expected values follow from the rules stated with FiConvLaunch in include/fi_capi.h (tile counts in the
+    comments); tests/test_gpu_conv32_edges.py holds the launches of its tables' shapes to the float64 reference."""
+    import ctypes
+    import test_gpu_conv32_edges as E
+    from feature_intertwiner_amd import _lib
+    L = _lib.load()
+    X, Wt, Y, G = 0x10000, 0x20000, 0x30000, 0x40000
+
+    def fwd(N, Cin, H, W, Cout, R, stride, pad, layout, ol=0, y=Y, gate=None):
+        planned = _lib.planned_launches(L.fi_conv2d_forward_launches, X, Wt, None, None, None, gate, y, N, Cin, H, W, Cout, R, R,
+                                        stride, stride, pad, pad, 0, layout, 0, 0, ol)
+        return [E.launch_summary(p) for p in planned], [(p.p_base, p.pixels) for p in planned]
+
+    def row(name, **kw):
+        return fwd(*E.FWD[name][:9], **kw)[0]
+
+    # every forward row of the GPU table: the plan the GPU test asserts before it launches, here without a device
+    for name in E.FWD:
+        for ol in (0, 1) if name in E.FWD_LAUNCH_CL else (0,):
+            expect, ranges = E.expected_launches(name, ol)
+            got = fwd(*E.FWD[name][:9], ol=ol)
+            assert got[0] == expect and (ranges is None or got[1] == ranges), (name, ol, got)
+    # tail launch: 513 x 2 = 1026 tiles of 128 x 128 -> 512 x 2 tiles over 65536 pixels + 128 pixels on 64 x 64 tiles at
+    # p_base 65536; K = 96 < 128 keeps the plain tile order.  1024 tiles: one launch
+    tail = ("GENERIC", 64, 64, "tap_major vec_out", 2, 4)
+    assert fwd(1, 96, 216, 304, 256, 1, 1, 0, 1) == ([("GENERIC", 128, 128, "tap_major vec_out", 512, 2), tail],
+                                                     [(0, 65536), (65536, 128)])
+    assert fwd(1, 96, 256, 256, 256, 1, 1, 0, 1) == ([("GENERIC", 128, 128, "tap_major vec_out", 512, 2)], [(0, 65536)])
+    # ... with a swizzled main launch (3x3: nx 512, already a multiple of 8); without a tail 513 tiles pad to 520; the
+    # generic_bm128 row (nx 256) is the unswizzled side
+    assert fwd(1, 16, 432, 608, 256, 3, 2, 1, 1) == ([("GENERIC", 128, 128, "tap_major vec_out swizzled", 512, 2), tail],
+                                                     [(0, 65536), (65536, 128)])
+    assert fwd(1, 16, 432, 608, 128, 3, 2, 1, 1)[0] == [("GENERIC", 128, 128, "tap_major vec_out swizzled", 520, 1)]
+    assert "swizzled" not in row("generic_bm128")[0][3]
+    # 64-pixel tiles: fewer than 1024 workgroups of 64 x 128 (patch_nb: 120 x 4); not at 1024, not below 64 pixels
+    assert row("patch_nb") == [("GENERIC", 64, 64, "tap_major vec_out", 240, 4)]
+    assert fwd(1, 64, 256, 512, 64, 1, 1, 0, 1)[0] == [("GENERIC", 64, 128, "tap_major vec_out", 1024, 1)]
+    assert fwd(1, 16, 4, 4, 64, 3, 1, 1, 1)[0] == [("GENERIC", 64, 128, "tap_major vec_out", 1, 1)]
+    # vector epilogue: needs OH * OW % 4 == 0 (reg1x1_nb_hw: 127 x 129) and a 16-byte aligned y
+    assert "vec_out" in row("patch_nb")[0][3] and "vec_out" not in row("reg1x1_nb_hw")[0][3]
+    assert row("patch_nb", y=Y + 4) == [("GENERIC", 64, 64, "tap_major", 240, 4)]
+    # row-major weights (7x7 is instantiated for them alone), channels-last output, the flat kernel's 13 / 14 patch rows
+    assert row("stem") == [("GENERIC", 64, 128, "vec_out", 16, 1)]
+    assert _lib.WINDOWS[_lib.planned_launches(L.fi_conv2d_forward_launches, X, Wt, None, None, None, None, Y, 2, 3, 64, 64, 64, 7, 7,
+                                              2, 2, 3, 3, 0, 0, 0, 0, 0)[0].window] == "7x7"
+    assert _lib.WINDOWS[_lib.planned_launches(L.fi_conv2d_forward_launches, X, Wt, None, None, None, None, Y, 2, 16, 64, 64, 64, 7, 7,
+                                              2, 2, 3, 3, 0, 1, 0, 0, 0)[0].window] == "other"      # tap-major 7x7: run-time window
+    assert row("patch_nb", ol=1) == [("GENERIC", 64, 128, "tap_major channels_last", 120, 4)]
+    assert row("flat14")[0][0] == "PATCH_FLAT13" and row("flat12")[0][0] == "PATCH_FLAT14"
+    # Winograd: the 14 x 14 instantiation on a flat slot, H and W at run time on a 2-D one (a row of
+    # tests/test_gpu_conv_wino2d.py); FI_NO_WINOGRAD, read per call, turns both into the direct form; 8-byte alignment of a gate
+    w14, w2d = (168, 64, 14, 14, 256, 3, 1, 1, 1), (1, 64, 128, 128, 256, 3, 1, 1, 1)
+    assert fwd(*w14)[0] == [("WINO14", 128, 128, "tap_major", 528, 1)]               # 8232 tiles: 258 groups of 32 -> 264, x 2
+    assert fwd(*w2d)[0] == [("WINO", 128, 128, "tap_major", 256, 1)]                 # 4096 tiles: 128 groups, x 2
+    assert _with_env("FI_NO_WINOGRAD", lambda: fwd(*w14)[0]) == [("PATCH_FLAT13", 128, 128, "tap_major", 528, 1)]
+    assert _with_env("FI_NO_WINOGRAD", lambda: fwd(*w2d)[0]) == [("PATCH", 128, 128, "tap_major vec_out", 256, 1)]
+    assert fwd(*w2d, gate=G + 8)[0][0][0] == "WINO" and fwd(*w2d, gate=G + 4)[0][0][0] == "PATCH"
+    assert _with_env("FI_NO_PATCH", lambda: fwd(*w2d)[0][0][0]) == "GENERIC"
+    assert _with_env("FI_NO_REG1X1", lambda: row("reg1x1")[0][0]) == "GENERIC" and row("reg1x1")[0][0] == "REG1X1"
+    assert fwd(1, 128, 128, 128, 256, 1, 1, 0, 3)[0][0][0] == "RING"
+
+    # weight gradient: the form and flags of every row of the GPU table
+    def wgrad(name, n=1, flags=0):
+        N, Cin, H, W, Cout, k, st, pd, layout = E.WGRAD[name][:9]
+        (p,) = _lib.planned_launches(L.fi_conv2d_weight_grad_launch, X, Y, Wt, N, Cin, H, W, Cout, k, k, st, st, pd, pd, layout, None,
+                                     flags, n)
+        assert _lib.KERNEL_KEYS[p.kernel_id] == E.WGRAD[name][9] or n > 1
+        return (_lib.WGRAD_FORMS[p.form], {k for k in ("swizzled", "row_uniform") if p.flags & _lib.LAUNCH_FLAGS[k]}), p
+
+    for name in E.WGRAD:
+        assert wgrad(name)[0] == E.wgrad_form_and_flags(name), name
+    assert {E.wgrad_form_and_flags(n)[0] for n in E.WGRAD} == set(_lib.WGRAD_FORMS)
+    # the 1-D XCD-aware grid: from 32768 pixels (unless FI_NO_WG_SWZ) and for any batch, whatever the switch
+    assert "swizzled" in wgrad("vec_swizzled")[0][1] and "swizzled" not in wgrad("bm128")[0][1]              # 24576 pixels
+    assert "swizzled" not in _with_env("FI_NO_WG_SWZ", lambda: wgrad("vec_swizzled"))[0][1]
+    for name in ("vec_3x3", "vec_swizzled"):
+        both, p = _with_env("FI_NO_WG_SWZ", lambda: wgrad(name, n=5, flags=_lib.OUTPUTS_ZEROED))
+        assert "swizzled" in both[1] and p.per_launch == 5, name
+    assert "swizzled" not in wgrad("vec_3x3", n=5)[0][1] and wgrad("half_3x3", n=5, flags=_lib.OUTPUTS_ZEROED)[1].per_launch == 1
+    # the launch query and the older readers agree: tile rows, grid = column tiles x Cout tiles x splits
+    p = wgrad("vec_partial_split")[1]
+    assert (p.tile_rows, p.window, p.grid_x, p.grid_y, p.grid_z, p.splits, p.pixels_per_split) == (64, 1, 9, 2, 3, 3, 400)
+    # fi_gemm_nt: the vector form on the K of tests/test_gpu_conv_plan.py::test_flop_log_gemm
+    for K, rows_, splits, pps in ((24576, 128, 48, 512), (20480, 64, 32, 640)):
+        (p,) = _lib.planned_launches(L.fi_gemm_nt_launch, X, Wt, None, None, Y, 256, 1024, K, 0, G)
+        assert (_lib.WGRAD_FORMS[p.form], p.tile_rows, p.splits, p.pixels_per_split) == ("VEC", rows_, splits, pps)
+        assert (p.grid_x, p.grid_y, p.grid_z) == (8, 256 // rows_, splits) and p.flags == 1 | 16      # tap-major, row-uniform
+    # rejected argument lists: the same status as the launch entry, nothing written
+    a = [16, 16, None, None, None, 32, 16]
+    out, n = (_lib.ConvLaunch * 2)(), ctypes.byref(ctypes.c_int(-1))
+    bad = (1, 32, 8, 8, 64, 3, 3, 1, 1, 1, 1, 0, 5, 0, 0, 0)
+    assert L.fi_conv2d_forward_launches(*a, *bad, out, n) == L.fi_conv2d_forward_live(*a, *bad, None, None) == -1
+    assert L.fi_conv2d_forward_launches(*a, *bad[:12], 1, 0, 0, 0, None, None) == -1
+    w = (16, 16, 16, 1, 32, 8, 8, 64, 3, 3, 1, 1, 1, 1, 1, None, 0)
+    assert L.fi_conv2d_weight_grad_launch(*w, 1, out) == L.fi_conv2d_weight_grad(*w, None) == -1
+    assert L.fi_conv2d_weight_grad_launch(*w[:14], 0, None, 0, 0, out) == -1 and L.fi_conv2d_weight_grad_launch(*w, 1, None) == -1
+    g = (16, 16, None, None, 16, 8, 100, 64, 0, 16)
+    assert L.fi_gemm_nt_launch(*g, out) == L.fi_gemm_nt_affine(*g, None, None) == -1
+
+
+def test_fp32_launchers_only_dispatch():
+    """Every threshold, alignment test and environment switch of the fp32 convolutions lives in the planners of
+    csrc/conv_igemm.hip: launch_fwd, launch_wgrad and fi_conv2d_forward_live behind its plan_forward call hold none."""
+    src = open(os.path.join(ROOT, "feature_intertwiner_amd", "csrc", "conv_igemm.hip")).read()
+
+    def body(signature, start_after=None):
+        at = src.index(signature)
+        i, depth = src.index("{", src.index(")", at)), 0
+        for j in range(i, len(src)):
+            depth += {"{": 1, "}": -1}.get(src[j], 0)
+            if depth == 0:
+                text = src[i:j + 1]
+                return text[text.index(start_after):] if start_after else text
+        raise AssertionError(signature)
+
+    bodies = {"launch_fwd": body("void launch_fwd("), "launch_wgrad_bm": body("void launch_wgrad_bm("),
+              "launch_wgrad": body("void launch_wgrad("),
+              "fi_conv2d_forward_live": body("int fi_conv2d_forward_live(", start_after="plan_forward(")}
+    for name, text in bodies.items():
+        assert "hipLaunchKernelGGL" in text or "launch_wgrad_bm" in text, name
+        for token in ("getenv", "% 16 == 0", "1024", "32768", ">= 512", "rem * 3"):
+            assert token not in text, (name, token)
+
+
 def test_16bit_forward_plan_names_the_variant_on_both_sides_of_every_threshold():
     """fi_conv2d_forward_plan_{bf16,f16} is the planner of fi_conv2d_forward_live_{bf16,f16} run on the host: aligned fake
     pointer values, shapes on both sides of every threshold of csrc/conv_bf16.hip (tile counts in the comments: 8 x 16 or

@@ -51,7 +51,48 @@ FWD = {
     "generic_bm128": (1, 16, 512, 256, 256, 3, 2, 1, 1, "conv_fwd_bm128_3x3"),       # 512 tiles of 128 x 128
     "generic_bm64": (1, 16, 508, 256, 256, 3, 2, 1, 1, "conv_fwd_bm64_3x3"),         # 508
     "stem": (2, 3, 64, 64, 64, 7, 2, 3, 0, "conv_fwd_bm64_7x7"),                     # weight_layout 0
+    # the generic kernel's launch plan: 513 x 2 = 1026 tiles of 128 x 128 are a main launch of 512 x 2 and a tail of 128
+    # pixels on 64 x 64 tiles; 513 pixel tiles in the XCD-aware order are a grid padded to 520; 16 pixels are one tile
+    "tail": (1, 96, 216, 304, 256, 1, 1, 0, 1, "conv_fwd_bm128_1x1"),                # K = 96 < 128: plain tile order
+    "tail_swizzled": (1, 16, 432, 608, 256, 3, 2, 1, 1, "conv_fwd_bm128_3x3"),       # the main launch swizzled, nx 512
+    "swizzled_pad": (1, 16, 432, 608, 128, 3, 2, 1, 1, "conv_fwd_bm128_3x3"),        # 513 x 1 tiles, no tail
+    "tiny": (1, 16, 4, 4, 64, 3, 1, 1, 1, "conv_fwd_bm64_3x3"),                      # P = 16 < 64: no 64-pixel tiles
 }
+# name -> what fi_conv2d_forward_launches plans for the shape's first (or only) launch with NCHW output and 16-byte aligned
+# operands: (form, tile rows, tile pixels, flags, grid x, grid y); _lib.FWD_FORMS / LAUNCH_FLAGS name forms and flags
+FWD_LAUNCH = {
+    "patch": ("PATCH", 128, 128, "tap_major vec_out", 256, 1),
+    "patch_nb": ("GENERIC", 64, 64, "tap_major vec_out", 240, 4),                    # 480 workgroups < 1024: 64-pixel tiles
+    "patch_straddle": ("PATCH", 128, 128, "tap_major vec_out", 272, 1),              # 136 pixel tiles x 2
+    "patch_cout160": ("PATCH", 128, 128, "tap_major vec_out", 256, 1),
+    "flat14": ("PATCH_FLAT13", 128, 128, "tap_major", 528, 1),                       # 258 pixel tiles padded to 264, x 2
+    "flat14_nb": ("GENERIC", 64, 64, "tap_major vec_out", 509, 4),
+    "flat14_h7": ("PATCH_FLAT13", 128, 128, "tap_major", 528, 1),
+    "flat12": ("PATCH_FLAT14", 128, 128, "tap_major vec_out", 512, 1),
+    "flat12_nb": ("GENERIC", 64, 64, "tap_major vec_out", 509, 4),
+    "flat12_h10": ("PATCH_FLAT14", 128, 128, "tap_major vec_out", 512, 1),
+    "dgrad_patch": ("PATCH", 128, 128, "tap_major vec_out", 256, 1),
+    "dgrad_flat14": ("PATCH_FLAT13", 128, 128, "tap_major", 528, 1),
+    "dgrad_flat12": ("PATCH_FLAT14", 128, 128, "tap_major vec_out", 512, 1),
+    "reg1x1": ("REG1X1", 128, 128, "tap_major vec_out", 256, 1),
+    "reg1x1_nb_tiles": ("GENERIC", 64, 64, "tap_major vec_out", 248, 4),
+    "reg1x1_nb_cin": ("GENERIC", 64, 64, "tap_major vec_out", 256, 4),
+    "reg1x1_nb_hw": ("GENERIC", 64, 64, "tap_major", 256, 4),                        # H * W % 4 != 0: scalar epilogue
+    "generic_bm128": ("GENERIC", 128, 128, "tap_major vec_out", 256, 2),             # nx 256 < 512: plain tile order
+    "generic_bm64": ("GENERIC", 64, 64, "tap_major vec_out", 508, 4),
+    "stem": ("GENERIC", 64, 128, "vec_out", 16, 1),                                  # row-major weights: no 64-pixel form
+    "tail": ("GENERIC", 128, 128, "tap_major vec_out", 512, 2),
+    "tail_swizzled": ("GENERIC", 128, 128, "tap_major vec_out swizzled", 512, 2),
+    "swizzled_pad": ("GENERIC", 128, 128, "tap_major vec_out swizzled", 520, 1),
+    "tiny": ("GENERIC", 64, 128, "tap_major vec_out", 1, 1),
+}
+# ... with channels-last output (test_forward_channels_last_output)
+FWD_LAUNCH_CL = {
+    "patch": ("PATCH", 128, 128, "tap_major channels_last vec_out", 256, 1),
+    "patch_nb": ("GENERIC", 64, 128, "tap_major channels_last", 120, 4),             # no 64-pixel channels-last form
+}
+# the second launch of a main / tail pair, and (p_base, pixels) of the two: every pixel belongs to exactly one
+TAIL = {name: (("GENERIC", 64, 64, "tap_major vec_out", 2, 4), (0, 65536), (65536, 128)) for name in ("tail", "tail_swizzled")}
 FLAT = ["flat14", "flat14_h7", "flat12", "flat12_h10"]
 EPILOGUES = ["bias", "scale_bias", "residual", "gate", "relu", "all"]
 
@@ -94,8 +135,24 @@ def _epilogue_operands(name):
     return bias, scale, residual, gate
 
 
+def launch_summary(launch):
+    """(form, tile rows, tile pixels, flags, grid x, grid y) of a planned forward launch, as FWD_LAUNCH states it."""
+    from feature_intertwiner_amd import _lib
+    return (_lib.FWD_FORMS[launch.form], launch.tile_rows, launch.tile_pixels,
+            " ".join(k for k, bit in _lib.LAUNCH_FLAGS.items() if launch.flags & bit), launch.grid_x, launch.grid_y)
+
+
+def expected_launches(name, output_layout=0):
+    """[summary of every launch] and [(p_base, pixels)] (None for a single launch) that the tables state for a shape."""
+    first = (FWD_LAUNCH_CL if output_layout else FWD_LAUNCH)[name]
+    if name in TAIL and not output_layout:
+        return [first, TAIL[name][0]], list(TAIL[name][1:])
+    return [first], None
+
+
 def _fwd_launch(name, y, bias=None, scale=None, residual=None, gate=None, relu=0, output_layout=0):
-    """The planned key of the shape's launch, asserted, then the launch: fi_conv2d_forward_live, or _gated with a gate."""
+    """The planned key, form, tiles, flags and grid of the shape's launches, asserted, then the call:
+    fi_conv2d_forward_live, or _gated with a gate."""
     from feature_intertwiner_amd import _lib
     L = _lib.load()
     x, w = _fwd_problem(name)[:2]
@@ -104,6 +161,10 @@ def _fwd_launch(name, y, bias=None, scale=None, residual=None, gate=None, relu=0
             N, Cin, H, W, Cout, k, k, st, st, pd, pd, relu, layout, 0, 0, output_layout)
     key = _lib.planned_kernel(L.fi_conv2d_forward_plan, *args)
     assert key == expect, (name, key)
+    planned = _lib.planned_launches(L.fi_conv2d_forward_launches, *args)
+    summaries, ranges = expected_launches(name, output_layout)
+    assert [launch_summary(p) for p in planned] == summaries, (name, [launch_summary(p) for p in planned])
+    assert ranges is None or [(p.p_base, p.pixels) for p in planned] == ranges
     if gate is not None:
         _lib.check(L.fi_conv2d_forward_gated(*args, _lib.current_stream()), "fi_conv2d_forward_gated")
     else:
@@ -124,6 +185,8 @@ def test_forward_is_the_float64_reference_at_every_kernels_boundary(name):
     key = _fwd_launch(name, y)
     worst = R.check_bar(y, ref, mag, _dot(name), "%s (%s)" % (name, key))
     print("%s %s: %s, worst |d|/(2^-24 m) %.2f" % (name, FWD[name][:9], key, worst))
+    if name in TAIL:
+        assert not torch.isnan(y).any()          # the output started NaN-filled: main and tail launch wrote every pixel
 
 
 @pytest.mark.parametrize("kind", EPILOGUES)
@@ -193,8 +256,8 @@ def test_conv2d_backward_on_12_wide_maps(Cin):
 
 
 # ---- weight gradient ----------------------------------------------------------------------------------------------------
-# name -> (N, Cin, H, W, Cout, R, stride, pad, weight_layout, expected kernel key).  The comments name the branch of
-# launch_wgrad (csrc/conv_igemm.hip) the shape takes; the key tells tile height and window class apart.
+# name -> (N, Cin, H, W, Cout, R, stride, pad, weight_layout, expected kernel key).  The key tells tile height and window
+# class apart; the kernel form and its flags (fi_conv2d_weight_grad_launch) follow from the name, see wgrad_form_and_flags.
 WGRAD = {
     # row-major vector kernel (same-size stride-1 layer, H * W % 4 == 0, Cin % 128 == 0), the smallest maps it accepts
     "vec_3x3": (1, 128, 4, 4, 128, 3, 1, 1, 1, "conv_wgrad_bm64_3x3"),
@@ -232,6 +295,18 @@ WGRAD = {
 }
 # (splits, pixels per split) the library's query must answer for the partial-split rows
 PARTIAL_SPLIT = {"vec_partial_split": (3, 400), "half_partial_split": (3, 400), "scalar_partial_split": (3, 432)}
+
+
+def wgrad_form_and_flags(name):
+    """(_lib.WGRAD_FORMS name, {swizzled, row_uniform} flags) of a single-problem launch of a WGRAD row."""
+    form = {"vec": "VEC", "bm128": "VEC", "bm64": "VEC", "half": "VEC_TWO_TAP", "scalar": "SCALAR_TAP_MAJOR",
+            "strided": "SCALAR_TAP_MAJOR", "rowmajor": "SCALAR_ROW_MAJOR"}[name.split("_")[0]]
+    flags = set()
+    if name.endswith("_u16") or name in ("vec_swizzled", "bm128", "bm64"):          # OW % 16 == 0 on a vector form
+        flags.add("row_uniform")
+    if name == "vec_swizzled":                                                       # 32768 pixels
+        flags.add("swizzled")
+    return form, flags
 
 
 def _wgrad_operands(shape, seed):
@@ -272,6 +347,15 @@ def _wgrad_plan(x, dy, dw, db, shape, layout, flags, n=1):
     return _lib.KERNEL_KEYS[key], per, splits, pps
 
 
+def _wgrad_launch(x, dy, dw, db, shape, layout, flags, n=1):
+    """(form, {swizzled, row_uniform} flags) of the launch, from fi_conv2d_weight_grad_launch."""
+    from feature_intertwiner_amd import _lib
+    (p,) = _lib.planned_launches(_lib.load().fi_conv2d_weight_grad_launch, _lib.ptr(x), _lib.ptr(dy), _lib.ptr(dw), *_geom(shape),
+                                 layout, _lib.ptr(db), flags, n)
+    assert bool(p.flags & _lib.LAUNCH_FLAGS["tap_major"]) == (_lib.WGRAD_FORMS[p.form] != "SCALAR_ROW_MAJOR")
+    return _lib.WGRAD_FORMS[p.form], {k for k in ("swizzled", "row_uniform") if p.flags & _lib.LAUNCH_FLAGS[k]}
+
+
 @pytest.mark.parametrize("name", sorted(WGRAD))
 def test_weight_gradient_is_the_float64_reference_on_every_launch_branch(name):
     """fi_conv2d_weight_grad with dbias into NaN-filled outputs (the call clears them), and under FI_OUTPUTS_ZEROED without
@@ -286,6 +370,7 @@ def test_weight_gradient_is_the_float64_reference_on_every_launch_branch(name):
     dw, db = _nan(*stored), _nan(Cout)
     key, per, splits, pps = _wgrad_plan(x, dy, dw, db, shape, layout, 0)
     assert (key, per) == (expect, 1), (name, key, per)
+    assert _wgrad_launch(x, dy, dw, db, shape, layout, 0) == wgrad_form_and_flags(name), name
     if name in PARTIAL_SPLIT:
         assert (splits, pps) == PARTIAL_SPLIT[name] and (splits - 1) * pps < pixels < splits * pps, (name, splits, pps, pixels)
     _lib.check(L.fi_conv2d_weight_grad(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(dw), *_geom(shape), layout, _lib.ptr(db), 0,
@@ -317,6 +402,7 @@ def test_weight_gradient_batch_launch_against_float64():
     dbs = [torch.zeros(128, device=DEV) for _ in range(n)]
     key, per, splits, pps = _wgrad_plan(probs[0][0], probs[0][1], dws[0], dbs[0], shape, 1, _lib.OUTPUTS_ZEROED, n)
     assert (key, per) == ("conv_wgrad_bm64_3x3", n)
+    assert _wgrad_launch(probs[0][0], probs[0][1], dws[0], dbs[0], shape, 1, _lib.OUTPUTS_ZEROED, n) == ("VEC", {"swizzled"})
     arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
     _lib.prof_reset()
     _lib.prof_enable(True)

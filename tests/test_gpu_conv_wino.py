@@ -102,6 +102,16 @@ def _launch(name, y, x=None, bias=None, scale=None, residual=None, gate=None, re
     return _lib.prof_get(key)[0]
 
 
+def _form(name, y):
+    """The _lib.FWD_FORMS name of the one launch fi_conv2d_forward_launches plans for the shape."""
+    from feature_intertwiner_amd import _lib
+    x, w = _problem(name)[:2]
+    N, Cin, Cout, layout = SHAPES[name][:4]
+    (launch,) = _lib.planned_launches(_lib.load().fi_conv2d_forward_launches, _lib.ptr(x), _lib.ptr(w), None, None, None, None,
+                                      _lib.ptr(y), N, Cin, 14, 14, Cout, 3, 3, 1, 1, 1, 1, 0, layout, 0, 0, 0)
+    return _lib.FWD_FORMS[launch.form]
+
+
 def _direct(fn):
     """fn() with FI_NO_WINOGRAD=1 (the library reads it per call)."""
     old = os.environ.get("FI_NO_WINOGRAD")
@@ -167,9 +177,11 @@ def test_an_image_gives_the_same_bits_wherever_it_sits_in_the_batch():
 
 @pytest.mark.parametrize("name", ["w64", "w64_dgrad"])
 def test_the_winograd_form_ran(name):
-    """With and without FI_NO_WINOGRAD: the same key, one launch counted each, both within the bar, different bits."""
+    """With and without FI_NO_WINOGRAD: the planned form, the same key, one launch counted each, both within the bar,
+    different bits."""
     x, w, ref, mag = _problem(name)
     y_w, y_d = _nan(*ref.shape), _nan(*ref.shape)
+    assert _form(name, y_w) == "WINO14" and _direct(lambda: _form(name, y_d)) == "PATCH_FLAT13"
     assert _launch(name, y_w) == 1
     assert _direct(lambda: _launch(name, y_d)) == 1
     worst_w = R.check_bar(y_w, ref, mag, SHAPES[name][1] * 9, name + " winograd")

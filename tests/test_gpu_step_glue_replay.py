@@ -110,7 +110,8 @@ CHECKED_ELSEWHERE = {
 HOST_ONLY = {"fi_calib_copy", "fi_version", "fi_last_error", "fi_prof_enable", "fi_prof_reset", "fi_prof_get", "fi_prof_kernel_name",
              "fi_sgd_chunks", "fi_conv1x1_ring_eligible", "fi_conv2d_forward_plan", "fi_conv2d_weight_grad_plan", "fi_gemm_nt_plan",
              "fi_conv2d_forward_plan_bf16", "fi_conv2d_forward_plan_f16", "fi_conv2d_weight_grad_plan_bf16",
-             "fi_conv2d_weight_grad_plan_f16", "fi_conv2d_weight_grad_layout", "fi_conv2d_weight_grad_split_plan"}
+             "fi_conv2d_weight_grad_plan_f16", "fi_conv2d_weight_grad_layout", "fi_conv2d_weight_grad_split_plan",
+             "fi_conv2d_forward_launches", "fi_conv2d_weight_grad_launch", "fi_gemm_nt_launch"}
 
 
 def _conv_specs():

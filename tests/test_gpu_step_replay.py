@@ -70,7 +70,8 @@ def recorded_entry(name):
     """The launches the replay covers: every fi_conv* / fi_gemm_nt* entry except the host-side queries."""
     return (name.startswith("fi_conv") or name.startswith("fi_gemm_nt")) and \
         not name.endswith("_eligible") and not name.endswith("_workspace_bytes") and \
-        not name.endswith("_plan") and "_plan_" not in name and not name.endswith("_layout")
+        not name.endswith("_plan") and "_plan_" not in name and not name.endswith("_layout") and \
+        not name.endswith("_launch") and not name.endswith("_launches")
 
 
 def lowp_dtype(name):
