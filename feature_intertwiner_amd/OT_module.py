@@ -26,7 +26,7 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .conv import Conv1d, Conv2d
+from .conv import Conv1d, Conv2d, ConvTranspose3x3
 
 EPS = 1e-20
 
@@ -187,7 +187,7 @@ def _generator(ch_x, ch_y, two_dim, upsample):
     if not two_dim:
         return nn.Sequential(Conv1d(ch_x, ch_y, kernel_size=3, padding=1, stride=1), nn.ReLU())
     stride, out_pad = (2, 1) if upsample else (1, 0)
-    return nn.Sequential(nn.ConvTranspose2d(ch_x, ch_y, kernel_size=3, padding=1, stride=stride, output_padding=out_pad),
+    return nn.Sequential(ConvTranspose3x3(ch_x, ch_y, kernel_size=3, padding=1, stride=stride, output_padding=out_pad),
                          nn.BatchNorm2d(ch_y), nn.ReLU())
 
 

@@ -33,6 +33,10 @@ COCOMASK_HEADERS = [os.path.join("..", "..", "include", "fi_cocomask.h")]
 OT_LIB_PATH = os.path.join(_HERE, "libfi_ot.so")
 OT_SOURCES = ["sinkhorn_bp.hip"]
 OT_HEADERS = SINKHORN_HEADERS + [os.path.join("..", "..", "include", "fi_ot.h")]
+# the transposed 3x3 / stride 2 convolution of the 2x make-up layer (include/fi_convt.h): a sixth library, built the same way
+CONVT_LIB_PATH = os.path.join(_HERE, "libfi_convt.so")
+CONVT_SOURCES = ["conv_transpose.hip"]
+CONVT_HEADERS = [os.path.join("..", "..", "include", "fi_convt.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
@@ -72,8 +76,8 @@ def _compile(sources, headers, force, verbose):
 
 
 def build_hip(force=False, verbose=False):
-    """Builds libfi_hip.so, libfi_eval.so, libfi_cocoeval.so, libfi_cocomask.so and libfi_ot.so; returns the path of the
-    first."""
+    """Builds libfi_hip.so, libfi_eval.so, libfi_cocoeval.so, libfi_cocomask.so, libfi_ot.so and libfi_convt.so; returns the
+    path of the first."""
     objs = _compile(SOURCES, HEADERS, force, verbose)
     if force or _stale(LIB_PATH, objs):
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
@@ -83,7 +87,8 @@ def build_hip(force=False, verbose=False):
     for lib, sources, headers in ((EVAL_LIB_PATH, EVAL_SOURCES, EVAL_HEADERS),
                                   (COCOEVAL_LIB_PATH, COCOEVAL_SOURCES, COCOEVAL_HEADERS),
                                   (COCOMASK_LIB_PATH, COCOMASK_SOURCES, COCOMASK_HEADERS),
-                                  (OT_LIB_PATH, OT_SOURCES, OT_HEADERS)):
+                                  (OT_LIB_PATH, OT_SOURCES, OT_HEADERS),
+                                  (CONVT_LIB_PATH, CONVT_SOURCES, CONVT_HEADERS)):
         objs = _compile(sources, HEADERS + headers, force, verbose)
         if force or _stale(lib, objs + [LIB_PATH]):
             cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + [

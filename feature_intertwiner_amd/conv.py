@@ -1,6 +1,6 @@
 """Dense convolution layers of the detector on the MI355X matrix cores.
 
-`Conv2d`, `ConvTranspose2x2` and `Conv1d` are drop-in subclasses of the torch modules
+`Conv2d`, `ConvTranspose2x2`, `ConvTranspose3x3` and `Conv1d` are drop-in subclasses of the torch modules
 (same constructor, same parameter names and shapes -> state dicts of the reference load
 unchanged) whose forward/backward run the hand-written fp32 MFMA implicit-GEMM kernels of
 csrc/conv_igemm.hip:
@@ -231,11 +231,13 @@ def _interleave2(classes, add, N, C, H, W, gate=None):
     return dx
 
 
-def _strided_dgrad(dz, w, in_hw, stride, padding, precision=None, add=None):
+def _strided_dgrad(dz, w, in_hw, stride, padding, precision=None, add=None, bias=None, scale=None, relu=False):
     """Data gradient of a strided convolution WITHOUT zero-stuffing: the input positions split into
     stride_h*stride_w residue classes; each class is a stride-1 correlation of dz with the sub-kernel
     of the taps that reach it (e.g. 3x3/stride 2/pad 1: 1, 2, 2 and 4 taps instead of 9 everywhere).
-    Stride 2: the class results are interleaved (and `add` added) by one kernel; other strides: strided copies."""
+    Stride 2: the class results are interleaved (and `add` added) by one kernel; other strides: strided copies.
+    bias / scale [Cin], relu: the epilogue of every class launch, act(. * scale + bias) -- the same arithmetic read as
+    a transposed convolution's FORWARD (_convt_compose); every element belongs to exactly one class."""
     N, Cout = dz.shape[0], dz.shape[1]
     Cin, R, S = w.shape[1], w.shape[2], w.shape[3]
     H, W = in_hw
@@ -257,7 +259,8 @@ def _strided_dgrad(dz, w, in_hw, stride, padding, precision=None, add=None):
             # (Indexing with Python lists would build index tensors on the host: a synchronising copy each.)
             k = w[:, :, r0:r0 + sh * (Th - 1) + 1:sh, s0:s0 + sw * (Tw - 1) + 1:sw].flip(2, 3)
             k = k.transpose(0, 1).contiguous()                                  # [Cin, Cout, Th, Tw]
-            out = _conv_fwd(dz, k, None, (1, 1), (pad_h, pad_w), out_hw=(qa, qb), precision=precision)
+            out = _conv_fwd(dz, k, bias, (1, 1), (pad_h, pad_w), relu=relu, scale=scale, out_hw=(qa, qb),
+                            precision=precision)
             if two:
                 classes[(a, b)] = out
             else:
@@ -1668,3 +1671,190 @@ class Conv1d(nn.Conv1d):
                 and self.dilation == (1,) and self.groups == 1:
             return linear(x[:, :, 0].contiguous(), self.weight[:, :, 1], self.bias).unsqueeze(2)
         return super(Conv1d, self).forward(x)
+
+
+# ---- transposed 3x3 convolution: the 2x make-up layer and the 2-D OptTrans generator ----------------------------------
+# nn.ConvTranspose2d(C, C, 3, stride=2, padding=1, output_padding=1) (lib/sub_module.py:312-314 at DEV.UPSAMPLE_FAC = 2,
+# lib/OT_module.py:24-36) on the library's own kernels.  Forward: ONE launch of csrc/conv_transpose.hip (libfi_convt.so,
+# include/fi_convt.h) computes the four output parity classes, folded eval-BatchNorm and ReLU included, and writes the
+# result interleaved (NCHW or channels-last).  Shapes that kernel does not take (Cin % 16 != 0) run the four-class
+# composition of existing kernels -- _strided_dgrad's arithmetic: the layer IS the data gradient of a 3x3 / stride 2 /
+# pad 1 convolution whose [Cout, Cin, 3, 3] weight is this layer's [Cin_T, Cout_T, 3, 3] parameter as stored.
+# Backward, existing entry points only: dx is that convolution's forward of dy, dw its weight gradient with dy in the
+# input role and x in the output-gradient role (already in the parameter's layout), the ReLU mask, BatchNorm scale and
+# per-channel sums one fi_bn_act_backward pass.  Always fp32, whatever MODEL.CONV_PRECISION says.
+CONVT_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfi_convt.so")
+_cp, _ci = ctypes.c_void_p, ctypes.c_int
+# name -> (restype, argtypes); mirrors include/fi_convt.h one to one
+CONVT_SIGNATURES = {
+    "fi_conv_transpose3x3s2_eligible": (_ci, [_ci, _ci, _ci, _ci, _ci, _ci, _cp, _cp]),
+    "fi_conv_transpose3x3s2_forward": (_ci, [_cp, _cp, _cp, _cp, _cp, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _cp]),
+}
+_convt = None
+CONVT_COMPOSE_ONLY = False        # True: eligible shapes take the four-class composition too (tests, scripts/convt_probe.py)
+
+
+def load_convt():
+    """Load libfi_convt.so (after libfi_hip.so, which it links against) and attach the signatures."""
+    global _convt
+    if _convt is not None:
+        return _convt
+    _lib.load()
+    if not os.path.exists(CONVT_LIB_PATH):
+        raise _lib.FiError("libfi_convt.so not found at %s -- build it with `python -m feature_intertwiner_amd.build` "
+                           "(there is no CPU/PyTorch fallback)" % CONVT_LIB_PATH)
+    L = ctypes.CDLL(CONVT_LIB_PATH)
+    for name, (res, args) in CONVT_SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype = res
+        fn.argtypes = args
+    _convt = L
+    return L
+
+
+def _convt_compose(x, w, bias, scale, relu):
+    """The four-class composition (the native route for shapes the fused kernel does not take): _strided_dgrad's
+    arithmetic applied to x with w [Cin, Cout, 3, 3] viewed as the weight of the equivalent stride-2 convolution -- four
+    stride-1 convolutions with scale / bias / ReLU in their epilogues, then fi_stride2_interleave."""
+    return _strided_dgrad(x, w, (2 * x.shape[2], 2 * x.shape[3]), (2, 2), (1, 1), precision="fp32", bias=bias,
+                          scale=scale, relu=relu)
+
+
+def _convt_fwd(x, w, bias, scale, relu, out_cl):
+    """act(conv_transpose(x, w) * scale + bias) for the 3x3 / stride 2 / padding 1 / output_padding 1 geometry;
+    out_cl: the result in torch.channels_last memory format."""
+    N, Cin, H, W = x.shape
+    Cout = w.shape[1]
+    L = load_convt()
+    fmt = torch.channels_last if out_cl else torch.contiguous_format
+    y = torch.empty((N, Cout, 2 * H, 2 * W), device=x.device, dtype=torch.float32, memory_format=fmt)
+    if N == 0:
+        return y
+    if not CONVT_COMPOSE_ONLY and L.fi_conv_transpose3x3s2_eligible(N, Cin, H, W, Cout, 1 if out_cl else 0, _lib.ptr(x),
+                                                                    _lib.ptr(y)) == 1:
+        with torch.cuda.device(x.device):
+            _lib.check(L.fi_conv_transpose3x3s2_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(scale),
+                                                        _lib.ptr(y), N, Cin, H, W, Cout, 1 if relu else 0,
+                                                        1 if out_cl else 0, _lib.current_stream()),
+                       "fi_conv_transpose3x3s2_forward")
+        return y
+    y = _convt_compose(x, w, bias, scale, relu)
+    return y.contiguous(memory_format=torch.channels_last) if out_cl else y
+
+
+class _ConvT3x3s2Fn(torch.autograd.Function):
+    """y = act(BN_eval(conv_transpose(x, w) + b)) (gamma None: y = act(conv_transpose(x, w) + b)), one launch."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, gamma, beta, mean, var, eps, relu, out_cl, fold):
+        _lib.require_cuda(x, w)
+        x = x.contiguous().float()
+        w = w.contiguous().float()
+        fused = gamma is not None
+        if not fused:
+            scale, shift = None, (b.contiguous().float() if b is not None else None)
+        elif fold is not None:            # precomputed for the whole model by refresh_bn_folds()
+            scale, shift = fold
+        else:
+            scale = gamma * torch.rsqrt(var + eps)
+            shift = beta - mean * scale
+            if b is not None:
+                shift = shift + b * scale
+            scale, shift = scale.contiguous(), shift.contiguous()
+        y = _convt_fwd(x, w, shift, scale, relu, out_cl)
+        ctx.conf = (fused, bool(relu), bool(out_cl), b is not None)
+        ctx.save_for_backward(x, w, y if (fused or relu) else None, scale, gamma, beta)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, y, scale, gamma, beta = ctx.saved_tensors
+        fused, relu, out_cl, has_bias = ctx.conf
+        need = ctx.needs_input_grad
+        L = _lib.load()
+        N, C, OH, OW = dy.shape
+        Cin, H, W = x.shape[1], x.shape[2], x.shape[3]
+        dx = dw = db = dgamma = dbeta = None
+        want_db = has_bias and need[2]
+        if fused or relu or want_db:
+            # ReLU mask, BatchNorm scale and the per-channel sums in one pass; a channels-last dy (the RoIAlign backward's)
+            # is transposed to NCHW on the way: dz feeds the NCHW convolution kernels
+            dy = dy.float().contiguous(memory_format=torch.channels_last) if out_cl else dy.contiguous().float()
+            dz = torch.empty((N, C, OH, OW), device=dy.device, dtype=torch.float32)
+            sums = torch.empty(3 * C, device=dy.device, dtype=torch.float32)
+            dshift = sums[:C]
+            dg = sums[C:2 * C] if (fused and need[3]) else None
+            dcb = sums[2 * C:] if (fused and want_db) else None
+            with torch.cuda.device(dy.device):
+                # (without a ReLU and without dgamma the pass reads y only into a sum it drops: dy stands in)
+                _lib.check(L.fi_bn_act_backward(_lib.ptr(dy), _lib.ptr(y if y is not None else dy),
+                                                _lib.ptr(scale if fused else _ones(C, dy.device)), _lib.ptr(gamma),
+                                                _lib.ptr(beta), None, N, C, OH * OW, 1 if relu else 0, _lib.ptr(dz), None,
+                                                _lib.ptr(dshift), _lib.ptr(dg), _lib.ptr(dcb), 1 if out_cl else 0, 0,
+                                                _lib.current_stream()), "fi_bn_act_backward")
+            if fused:
+                dgamma, dbeta, db = dg, (dshift if need[4] else None), dcb
+            else:
+                db = dshift if want_db else None
+        else:
+            dz = dy.contiguous().float()
+        if need[0]:
+            # the 3x3 / stride 2 / pad 1 convolution whose [out = Cin_T, in = Cout_T, 3, 3] weight is w as stored
+            dx = _conv_fwd(dz, w, None, (2, 2), (1, 1), precision="fp32")
+        if need[1]:
+            # ... and its weight gradient, dz in the input role, x in the output-gradient role: [Cin_T, Cout_T, 3, 3]
+            dw = torch.empty(w.shape, device=w.device, dtype=torch.float32)
+            with torch.cuda.device(dz.device):
+                _lib.check(L.fi_conv2d_weight_grad(_lib.ptr(dz), _lib.ptr(x), _lib.ptr(dw), N, C, OH, OW, Cin, 3, 3, 2, 2,
+                                                   1, 1, 0, None, 0, _lib.current_stream()), "fi_conv2d_weight_grad")
+        return dx, dw, db, dgamma, dbeta, None, None, None, None, None, None
+
+
+class ConvTranspose3x3(nn.ConvTranspose2d):
+    """nn.ConvTranspose2d(kernel_size=3, padding=1) of the make-up layer (lib/sub_module.py:312-314) and of the 2-D
+    OptTrans generator (lib/OT_module.py:24-36): same parameters and state-dict keys as the stock module.
+    stride 2 / output_padding 1: the fused four-class kernel (csrc/conv_transpose.hip), or the four-class composition of
+    existing kernels for shapes it does not take; stride 1 / output_padding 0: an ordinary 3x3 convolution with the weight
+    transposed and flipped (conv2d).  Inputs that are not fp32 on the GPU take the stock implementation."""
+
+    def geometry(self):
+        """2 or 1: the stride of the supported geometry this module has."""
+        if self.kernel_size != (3, 3) or self.padding != (1, 1) or self.groups != 1 or self.dilation != (1, 1) or \
+                getattr(self, "padding_mode", "zeros") != "zeros":
+            raise NotImplementedError("fi ConvTranspose3x3 supports kernel 3, padding 1, groups=1, dilation=1")
+        if self.stride == (2, 2) and self.output_padding == (1, 1):
+            return 2
+        if self.stride == (1, 1) and self.output_padding == (0, 0):
+            return 1
+        raise NotImplementedError("fi ConvTranspose3x3 supports stride 2 / output_padding 1 and stride 1 / output_padding 0")
+
+    def forward(self, x, output_size=None):
+        if not x.is_cuda or x.dtype != torch.float32:
+            return super(ConvTranspose3x3, self).forward(x, output_size)
+        if output_size is not None:
+            raise NotImplementedError("fi ConvTranspose3x3 takes no output_size")
+        if self.geometry() == 1:
+            # fp32 like the stride-2 form, whatever MODEL.CONV_PRECISION says (the forward records the setting it ran
+            # with for its backward)
+            global _PRECISION
+            prev, _PRECISION = _PRECISION, "fp32"
+            try:
+                return conv2d(x, self.weight.transpose(0, 1).flip(2, 3), self.bias, (1, 1), (1, 1))
+            finally:
+                _PRECISION = prev
+        return _ConvT3x3s2Fn.apply(x, self.weight, self.bias, None, None, None, None, 0.0, False, False, None)
+
+
+def convt_bn_act(x, conv, bn, relu=True, channels_last_out=False):
+    """act(bn(conv(x))) for a ConvTranspose3x3 and an eval-mode BatchNorm2d with running statistics: the stride-2 layer,
+    its folded BatchNorm and the ReLU in ONE launch (conv_bn_act's sibling; the fold is the cached one of
+    refresh_bn_folds).  A BatchNorm in training mode, the stride-1 geometry and inputs that are not fp32 on the GPU run
+    the module (bias only), then the stock BatchNorm and ReLU.  channels_last_out: the result in torch.channels_last
+    memory format, written that way by the kernel (for maps that only the channels-last RoIAlign reads)."""
+    if bn.training or not bn.track_running_stats or not x.is_cuda or x.dtype != torch.float32 or conv.geometry() != 2:
+        y = bn(conv(x))
+        y = F.relu(y) if relu else y
+        return y.contiguous(memory_format=torch.channels_last) if channels_last_out else y
+    _FOLD_PAIRS[bn] = conv
+    return _ConvT3x3s2Fn.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps,
+                               relu, bool(channels_last_out), _cached_fold(conv, bn))

@@ -17,8 +17,8 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import conv as _conv
-from .conv import (Conv2d, ConvTranspose2x2, GradBox, conv1x1_class_rows, conv2d, conv_bias_relu, conv_bn_act, linear,
-                   maxpool3x3s2, take_rows, upsample2x)
+from .conv import (Conv2d, ConvTranspose2x2, ConvTranspose3x3, GradBox, conv1x1_class_rows, conv2d, conv_bias_relu,
+                   conv_bn_act, convt_bn_act, linear, maxpool3x3s2, take_rows, upsample2x)
 from .intertwiner import class_mean, roi_level
 from .roi_align.crop_and_resize import CropAndResizeFunction, CropGradGroup, pyramid_crop_and_resize
 from .roi_pooling.functions.roi_pool import RoIPoolFunction
@@ -447,8 +447,7 @@ class Dev(nn.Module):
                 if config.DEV.UPSAMPLE_FAC == 1.:
                     conv_opt = Conv2d(depth, depth, kernel_size=3, padding=1)
                 elif config.DEV.UPSAMPLE_FAC == 2.:
-                    conv_opt = nn.ConvTranspose2d(depth, depth, kernel_size=3, stride=2, padding=1,
-                                                  output_padding=1)
+                    conv_opt = ConvTranspose3x3(depth, depth, kernel_size=3, stride=2, padding=1, output_padding=1)
                 n_up = 4 if config.DEV.MULTI_UPSAMPLER else 1
                 self.upsample = nn.ModuleList()
                 for _ in range(n_up):
@@ -523,6 +522,10 @@ class Dev(nn.Module):
                     take.taker = True
                 return conv_bn_act(m, seq[0], seq[1], relu=True, channels_last_out=(self.roi_type == 'roi_align'),
                                    dx_add_from=take, dx_give_to=give)
+            if isinstance(seq[0], ConvTranspose3x3):
+                # DEV.UPSAMPLE_FAC = 2: the transposed conv, its eval BatchNorm and the ReLU in one launch, channels-last
+                # for the same reason (a training-mode BatchNorm or a CPU map runs the three modules)
+                return convt_bn_act(m, seq[0], seq[1], relu=True, channels_last_out=(self.roi_type == 'roi_align'))
             return seq(m)
         return [make_up(i, m) for i, m in enumerate(x)]
 
