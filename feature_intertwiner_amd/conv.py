@@ -254,12 +254,20 @@ def _strided_dgrad(dz, w, in_hw, stride, padding, precision=None, add=None, bias
             if Th == 0 or Tw == 0:
                 continue
             pad_h, pad_w = Th - 1 - ch0, Tw - 1 - cw0
-            assert pad_h >= 0 and pad_w >= 0, "unsupported stride/padding combination"
+            src = dz
+            if pad_h < 0 or pad_w < 0:
+                # the class's first position is reached from output index c0 > T - 1 only (3x3 / stride 3 / pad 1, class
+                # 2: ih = 3q + 2 is read by tap 0 of output q + 1): the correlation starts -pad rows / columns into dz
+                src = dz[:, :, max(-pad_h, 0):, max(-pad_w, 0):]
+                pad_h, pad_w = max(pad_h, 0), max(pad_w, 0)
+                if src.shape[2] == 0 or src.shape[3] == 0:               # no output reaches the class
+                    continue
+                src = src.contiguous()
             # taps r0 + sh*t, t = Th-1 .. 0 (and the same along the width): a strided slice, reversed.
             # (Indexing with Python lists would build index tensors on the host: a synchronising copy each.)
             k = w[:, :, r0:r0 + sh * (Th - 1) + 1:sh, s0:s0 + sw * (Tw - 1) + 1:sw].flip(2, 3)
             k = k.transpose(0, 1).contiguous()                                  # [Cin, Cout, Th, Tw]
-            out = _conv_fwd(dz, k, bias, (1, 1), (pad_h, pad_w), relu=relu, scale=scale, out_hw=(qa, qb),
+            out = _conv_fwd(src, k, bias, (1, 1), (pad_h, pad_w), relu=relu, scale=scale, out_hw=(qa, qb),
                             precision=precision)
             if two:
                 classes[(a, b)] = out

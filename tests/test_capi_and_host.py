@@ -453,6 +453,35 @@ def test_16bit_forward_plan_names_the_variant_on_both_sides_of_every_threshold()
         assert query(X, Wt, None, None, None, None, None, Y, *ok, None) == -1
 
 
+def test_16bit_forward_plan_holds_the_edge_shape_table():
+    """Every row of tests/test_gpu_conv16_edges.py's CASES reaches the variant the table names, with a 16-bit weight copy
+    and without one, for both types: the planner run on the host with aligned fake pointer values.  The GPU file asserts
+    the same answers with its real pointers before every launch; a row that stops reaching its kernel fails here first."""
+    import ctypes
+    import test_gpu_conv16_edges as E
+    from feature_intertwiner_amd import _lib
+    L = _lib.load()
+    X, Wt, W16, Y = 0x10000, 0x20000, 0x30000, 0x40000
+    assert len(E.CASES) >= 50 and set(E.EPILOGUE_SHAPES) <= set(E.CASES)
+    for sfx in ("bf16", "f16"):
+        query = getattr(L, "fi_conv2d_forward_plan_" + sfx)
+        for name, row in E.CASES.items():
+            N, Cin, H, W, Cout, R, S, sh, sw, ph, pw, layout, out_hw, with_copy, without = row
+            oh, ow = out_hw if out_hw is not None else (0, 0)
+            got = []
+            for w16 in (W16, None):
+                v = ctypes.c_int(-1)
+                rc = query(X, Wt, w16, None, None, None, None, Y, N, Cin, H, W, Cout, R, S, sh, sw, ph, pw, 0, layout, oh, ow,
+                           0, ctypes.byref(v))
+                assert rc == 0, (sfx, name, rc)
+                got.append(_lib.CONV16_VARIANTS[v.value])
+            assert tuple(got) == (with_copy, without), (sfx, name, got)
+    # every fast variant and both generic tile heights are in the table, each fast one also with tap-reversed weights
+    for variant in ("PATCH_W16", "PATCH_FLAT_W16", "REG1X1_W16"):
+        assert {row[11] for row in E.CASES.values() if row[13] == variant} == {1, 2}, variant
+    assert {row[14] for row in E.CASES.values()} == {"GENERIC_BM64", "GENERIC_BM128", "PATCH"}
+
+
 def test_16bit_weight_grad_plan_names_the_variant_on_both_sides_of_every_threshold():
     """fi_conv2d_weight_grad_plan_{bf16,f16} is the planner of fi_conv2d_weight_grad_db_{bf16,f16} and of the batch entry
     run on the host: aligned fake pointer values, shapes on both sides of every threshold of the weight gradient's kernel

@@ -255,6 +255,13 @@ def test_conv2d_backward_on_12_wide_maps(Cin):
         Cin, {k: v[0] for k, v in used.items()}, worst_y, worst_dx, worst_dw))
 
 
+def test_strided_data_gradient_of_a_3x3_stride_3_layer():
+    """conv._strided_dgrad in fp32 on the row of tests/test_gpu_conv16_edges.py whose third residue class starts one row
+    and column into dz (a negative padding, which the function used to refuse)."""
+    from test_gpu_conv16_edges import check_strided_dgrad
+    print("3x3_s3_7x7 fp32: worst |d|/(2^-24 m) %.2f" % check_strided_dgrad("3x3_s3_7x7", "fp32"))
+
+
 # ---- weight gradient ----------------------------------------------------------------------------------------------------
 # name -> (N, Cin, H, W, Cout, R, stride, pad, weight_layout, expected kernel key).  The key tells tile height and window
 # class apart; the kernel form and its flags (fi_conv2d_weight_grad_launch) follow from the name, see wgrad_form_and_flags.
