@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib, grad_arena
+from . import _lib, grad_arena, step_state
 
 # bench.py sets this to a dict to accumulate the algorithmic flops (2*N*Cout*OH*OW*Cin*R*S) of
 # every launch, keyed by the device kernel instance (the library's fi_*_plan queries name it, see _log_flops).
@@ -130,12 +130,12 @@ def _conv_fwd(x, w, b, stride, padding, relu=False, scale=None, residual=None, o
         assert not out_channels_last and gate.shape == y.shape and gate.is_contiguous()
     if bf16:
         _log_flops("conv_bf16_fwd", flops)
-    if RING_1X1 and not bf16 and layout >= 1 and R * S == 1 and live is None and out_hw is None and not out_channels_last and _WF:
-        e = _WF.get(w.data_ptr())
-        if e is not None and e[3]() is not None and e[2] == (Cout, Cin) and (e[1] is None or e[1] == w._version) and \
+    if RING_1X1 and not bf16 and layout >= 1 and R * S == 1 and live is None and out_hw is None and not out_channels_last:
+        wf = _COPIES.lookup(w, step_state.FRAG, (Cout, Cin))
+        if wf is not None and \
                 L.fi_conv1x1_ring_eligible(N, Cin, H, W, Cout, 1, 1, stride[0], stride[1], padding[0], padding[1], 0,
                                            _lib.ptr(x), _lib.ptr(y), _lib.ptr(residual), _lib.ptr(gate)) == 1:
-            w, layout = e[0], 3         # the persistent 1x1 kernel (csrc/conv1x1_ring.hip)
+            w, layout = wf, 3           # the persistent 1x1 kernel (csrc/conv1x1_ring.hip)
     with torch.cuda.device(x.device):
         # live [1] int32 on the device, or None: only the first live[0] images are real (fi_conv2d_forward_live)
         args = (_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(scale), _lib.ptr(residual), _lib.ptr(gate), _lib.ptr(y),
@@ -563,11 +563,11 @@ def _weight_grad(x, w, dz, stride, padding, want_db=False, precision=None, bias_
         if db_into is not None:
             db_slot = db_into
         else:
-            db_slot, _ = _arena_take(("db", bias_ptr), Cout) if bias_ptr else (None, False)
+            db_slot, _ = _GRADS.take(("db", bias_ptr), Cout) if bias_ptr else (None, False)
     if want_db and db_slot is None:
         dw, first = None, False
     else:
-        dw, first = _arena_take(("dw", w.data_ptr()), Cout * Cin * R * S)
+        dw, first = _GRADS.take(("dw", w.data_ptr()), Cout * Cin * R * S)
         if dw is None:
             db_slot = None
         elif after_wgrad is not None and not first:
@@ -757,61 +757,33 @@ def _finish_wgrads():
     flush_deferred_wgrads()
 
 
-# ---- per-step derived state: W^T for the data gradient, zeroed gradient arena ---------------------
-_WT = {}           # weight data_ptr -> (W^T [Cin,R,S,Cout], weight version it was made from)
-_WF = {}           # data_ptr of a 1x1 weight (or of its W^T) -> (fragment-major copy, version or None, (Cout, Cin) of the matrix,
-                   # weak reference to the tensor that owns the address).  An entry is valid only while its owner lives: a
-                   # model that is garbage-collected leaves its entries behind (the plan is weakly keyed), and the allocator
-                   # hands the freed addresses to the next model's tensors -- same shape, same version counter
-_ARENA = {"buf": None, "slots": {}, "used": set()}
-_PLAN = weakref.WeakKeyDictionary()      # model -> cached layer lists / descriptor table
-
-
-_WB = {}           # tap-major fp32 weight data_ptr -> (bf16 copy, version, shape): refreshed once per step
+# ---- per-step derived state: copies of the weights (W^T, fragment-major, 16-bit), zeroed gradient arena ---------------
+# Both are keyed by raw device addresses; step_state.py has the one rule that says when a copy may be used (owner alive
+# and at that address, version, what the reader expects of the copy) and the slot rules of the arena.  Here: what is
+# published, and when.
+_COPIES = step_state.Registry()          # address of a weight or of a W^T -> the copies made of it
+_GRADS = step_state.GradArena()          # this step's zeroed gradient buffer and its slots
+_PLAN = weakref.WeakKeyDictionary()      # model -> _StepPlan
 
 
 def _cached_bf16(w, dtype=torch.bfloat16, make=True):
     """16-bit copy of a (contiguous, tap-major) fp32 weight, made once per (tensor, version).  Model weights and
-    their W^T are converted for ALL layers by one multi-tensor copy per step (_prepare_step fills the cache); anything
-    else (temporaries) is converted here -- or, with make=False, left alone: None.  The entry keeps `w` alive, so its
-    address cannot be handed to another tensor while the entry exists."""
-    e = _WB.get(w.data_ptr())
-    if e is not None and e[1] == w._version and e[0].numel() == w.numel() and e[0].dtype == dtype:
-        return e[0].view(w.shape) if e[0].shape != w.shape else e[0]
-    if not make:
-        return None
-    wb = w.to(dtype)
-    _WB[w.data_ptr()] = (wb, w._version, tuple(w.shape), w)
-    return wb
+    their W^T are converted for ALL layers by one multi-tensor copy per step (_refresh_lowp publishes them); anything
+    else (temporaries) is converted here -- or, with make=False, left alone: None.  The record pins a temporary, so its
+    address cannot be handed to another tensor while the record exists."""
+    wb = _COPIES.lookup(w, step_state.LOWP, (dtype, w.numel()))
+    if wb is None:
+        if not make:
+            return None
+        wb = w.to(dtype)
+        _COPIES.publish(w, step_state.LOWP, wb, (dtype, w.numel()), pinned=True)
+    return wb.view(w.shape) if wb.shape != w.shape else wb
 
 
 def _cached_wt(w, scaled=False):
     """This step's W^T [Cin][R][S][Cout] (prepare_step); scaled: the copy with the layer's eval-BatchNorm scale folded
     in (W^T[...][co] * scale[co]) -- a layer has one or the other."""
-    e = _WT.get(w.data_ptr())
-    if e is not None and e[3]() is not None and e[1] == w._version and e[2] == bool(scaled) and \
-            e[0].shape == (w.shape[1], w.shape[2], w.shape[3], w.shape[0]):
-        return e[0]
-    return None
-
-
-def _arena_take(key, numel, partner=None):
-    """(slot, first): the slot reserved for `key` in this step's arena (zeroed at the start of the step) and
-    whether this is its first use in the step.  A layer applied several times per step (the RPN on 5 levels, the
-    feature extractor on small and big boxes) ACCUMULATES all its gradient contributions in the one slot -- the
-    kernels add with atomics anyway -- and hands the slot to autograd only the first time (later calls return no
-    gradient for the parameter), so there is no per-use buffer, fill and add.  (None, False): no slot."""
-    slot = _ARENA["slots"].get(key)
-    if slot is None or _ARENA["buf"] is None or slot[1] != numel:
-        return None, False
-    owner = slot[2]()
-    if owner is None or owner.data_ptr() != key[1]:
-        return None, False        # the model this arena belongs to is gone and its address was reused
-    if partner is not None and len(slot) > 3 and slot[3] != partner:
-        return None, False        # a BatchNorm block laid out for another convolution's bias: private buffers instead
-    first = key not in _ARENA["used"]
-    _ARENA["used"].add(key)
-    return _ARENA["buf"][slot[0]:slot[0] + numel], first
+    return _COPIES.lookup(w, step_state.WT, (bool(scaled), w.shape))
 
 
 _TR_DESC = np.dtype([("src", "<u8"), ("dst", "<u8"), ("rows", "<i4"), ("cols", "<i4"), ("taps", "<i4"), ("pad", "<i4"),
@@ -819,12 +791,168 @@ _TR_DESC = np.dtype([("src", "<u8"), ("dst", "<u8"), ("rows", "<i4"), ("cols", "
 
 
 def invalidate_step_state():
-    _WT.clear()
-    _WF.clear()
-    _WB.clear()
-    _ARENA["buf"] = None
-    _ARENA["slots"] = {}
-    _ARENA["used"] = set()
+    _COPIES.clear()          # (bumps the epoch the plans compare)
+    _GRADS.arm({}, None)
+
+
+# kind "fwd": a copy of W, tr_index -1; "dgrad": of the layer's W^T, wts[tr_index]
+_Frag = collections.namedtuple("_Frag", "module weight kind copy tr_index")
+
+
+class _StepPlan(object):
+    """What prepare_step does for one model, decided once (_build_plan):
+      ptrs, precision, layout   what the plan depends on: parameter addresses, conv precision, gradient arena layout
+      convs                     the Conv2d layers that run as convolutions (not full_window)
+      tr, tr_weights, wts       the layers that get a W^T, their weights and their W^T tensors
+      frag                      [_Frag]: fragment-major copies for the persistent 1x1 kernel
+      desc, table, tiles        FiTransposeDesc records (tr, then frag), their device copy, total tile count
+      lowp_srcs, lowp_dsts      16-bit precisions: weights then W^T tensors, and their flat 16-bit copies
+      slots                     ("dw" | "db" | "bn", address) -> step_state.Slot of the gradient arena
+    and what it last published:
+      scales                    the row_scale column written into `table` (addresses of the BatchNorm folds)
+      wt_made, wt_serial        (epoch, versions) the W^T / fragment copies were made from; count of such launches
+      lowp_made                 (epoch, wt_serial, versions) the 16-bit copies were made from"""
+
+    def __init__(self, **fields):
+        self.scales = self.wt_made = self.lowp_made = None
+        self.wt_serial = 0
+        self.__dict__.update(fields)
+
+
+def _build_plan(model, dev):
+    """The _StepPlan of `model`.  Stores the weights with Cin % 16 == 0 channels-last and allocates the copies'
+    tensors; no library call."""
+    convs = [m for m in model.modules() if isinstance(m, Conv2d) and not m.full_window]
+    for m in convs:
+        w = m.weight
+        if w.shape[1] % 16 == 0 and w.shape[2] * w.shape[3] > 1 and \
+                not w.is_contiguous(memory_format=torch.channels_last):
+            w.data = w.data.contiguous(memory_format=torch.channels_last)
+    tr = [m for m in convs if (tuple(m.stride) == (1, 1) or m.weight.shape[2] * m.weight.shape[3] == 1) and
+          m.weight.shape[0] % 16 == 0 and
+          m.weight.shape[1] % 16 == 0 and m.weight.shape[2] * m.weight.shape[3] <= 64 and m.weight.requires_grad]
+    desc = np.zeros(len(tr), dtype=_TR_DESC)
+    wts, base = [], 0
+    for i, m in enumerate(tr):
+        co, ci, r, s_ = m.weight.shape
+        wt = torch.empty((ci, r, s_, co), device=dev, dtype=torch.float32)
+        wts.append(wt)
+        desc[i] = (m.weight.data_ptr(), wt.data_ptr(), co, ci, r * s_, 0, base, 0)
+        base += r * s_ * ((co + 31) // 32) * ((ci + 31) // 32)
+    # fragment-major copies of the 1x1 / stride-1 weights for the persistent 1x1 kernel (conv1x1_ring_kernel,
+    # weight_layout 3): W itself for the forward pass, W^T (with the eval-BatchNorm scale, like the plain W^T) for the
+    # data gradient -- extra descriptors of the SAME launch (flag 1 = fragment-major, flag 2 = no transpose)
+    frag = []
+    tr_index = {m: i for i, m in enumerate(tr)}
+    for m in convs:
+        co, ci, r, s_ = m.weight.shape
+        if r * s_ != 1 or tuple(m.stride) != (1, 1) or tuple(m.padding) != (0, 0) or _PRECISION in _LOWP:
+            continue
+        if co % 128 == 0 and ci % 32 == 0 and ci >= 128:
+            frag.append(_Frag(m, m.weight, "fwd", torch.empty(co * ci, device=dev, dtype=torch.float32), -1))
+        if m in tr_index and ci % 128 == 0 and co % 32 == 0 and co >= 128:
+            frag.append(_Frag(m, m.weight, "dgrad", torch.empty(co * ci, device=dev, dtype=torch.float32), tr_index[m]))
+    if frag:
+        extra = np.zeros(len(frag), dtype=_TR_DESC)
+        for i, f in enumerate(frag):
+            co, ci = f.weight.shape[0], f.weight.shape[1]
+            extra[i] = (f.weight.data_ptr(), f.copy.data_ptr(), co, ci, 1, 3 if f.kind == "fwd" else 1, base, 0)
+            base += ((co + 31) // 32) * ((ci + 31) // 32)
+        desc = np.concatenate([desc, extra])
+    table = torch.from_numpy(desc.view(np.uint8).copy()).to(dev) if len(desc) else None
+    lowp_srcs, lowp_dsts = [], []
+    if _PRECISION in _LOWP:
+        lowp_srcs = [m.weight for m in convs if m.weight.shape[1] % 32 == 0] + wts
+        lowp_dsts = [torch.empty(t.numel(), device=dev, dtype=_LOWP[_PRECISION][1]) for t in lowp_srcs]
+    # gradient slots: the model-wide arena layout (grad_arena.py) -- every trainable parameter has one, in
+    # bucket order; the kernels' keys are the weight's / the BatchNorm gamma's address
+    layout = grad_arena.get_layout(model)
+    slots = {}
+    for m in convs:
+        for tag, p in (("dw", m.weight), ("db", m.bias)):
+            if p is not None and p.requires_grad and p in layout.slot:
+                slots[(tag, p.data_ptr())] = step_state.Slot(*layout.slot[p], weakref.ref(p), None)
+    for bn in [m for m in model.modules() if isinstance(m, nn.BatchNorm2d)]:
+        if bn in layout.bn_slot:
+            # partner: the address of the convolution bias the layout paired with this BatchNorm -- by adjacency
+            # among a module's children; a caller that combines the BatchNorm with ANOTHER convolution must not
+            # have that one's bias gradient adopted as a view of this block
+            partner = layout.bn_partner.get(bn)
+            slots[("bn", bn.weight.data_ptr())] = step_state.Slot(layout.bn_slot[bn], 3 * bn.num_features,
+                                                                  weakref.ref(bn.weight),
+                                                                  partner.data_ptr() if partner is not None else 0)
+    return _StepPlan(ptrs=tuple(p.data_ptr() for p in model.parameters()), precision=_PRECISION, layout=layout,
+                     convs=convs, tr=tr, tr_weights=[m.weight for m in tr], wts=wts, frag=frag, desc=desc, table=table,
+                     tiles=base, lowp_srcs=lowp_srcs, lowp_dsts=lowp_dsts, slots=slots)
+
+
+def _plan_for(model, dev):
+    """The model's plan, rebuilt when something it was built for has changed."""
+    plan = _PLAN.get(model)
+    ptrs = tuple(p.data_ptr() for p in model.parameters())
+    if plan is None or plan.ptrs != ptrs or plan.layout.superseded or plan.precision != _PRECISION:
+        _COPIES.sweep()          # records of models that no longer exist
+        plan = _PLAN[model] = _build_plan(model, dev)
+    return plan
+
+
+def _refresh_transposes(plan, grad_on, dev):
+    """W^T and the fragment-major copies of all layers in ONE launch, if a weight or a BatchNorm fold changed."""
+    # fp32 training: W^T of a layer that is followed by an eval-mode BatchNorm carries the BatchNorm's scale
+    # (_ConvBnActFn.backward feeds the data-gradient kernel the unscaled masked gradient); the 16-bit kernels keep the
+    # plain W^T.  The pairs are known after the first forward pass (conv_bn_act registers them).
+    scales = [None] * len(plan.tr)
+    if grad_on and _FOLD_PAIRS:
+        by_conv = {c: b for b, c in _FOLD_PAIRS.items()}
+        for i, m in enumerate(plan.tr):
+            b = by_conv.get(m)
+            if b is not None and not b.training and getattr(b, "_fi_fold", None) is not None:
+                scales[i] = b
+    sig = tuple(0 if b is None else b._fi_fold[0].data_ptr() for b in scales)
+    sig = sig + tuple(sig[f.tr_index] if f.tr_index >= 0 else 0 for f in plan.frag)
+    if plan.scales != sig:
+        plan.desc["row_scale"] = sig
+        plan.table = torch.from_numpy(plan.desc.view(np.uint8).copy()).to(dev)
+        plan.scales = sig
+        plan.wt_made = None
+    versions = tuple(w._version for w in plan.tr_weights) + tuple(b._fi_fold[2] for b in scales if b is not None)
+    versions = versions + tuple(f.weight._version for f in plan.frag if f.tr_index < 0)
+    if plan.wt_made == (_COPIES.epoch, versions):
+        return
+    L = _lib.load()
+    with torch.cuda.device(dev):
+        _lib.check(L.fi_weight_transpose_batch(_lib.ptr(plan.table), len(plan.desc), plan.tiles,
+                                               _lib.current_stream()), "fi_weight_transpose_batch")
+    # once per training step: the last step's temporaries (16-bit copies made on the fly, with the fp32 tensors they
+    # pin) go first, before anything is published into a record one of them opened.  The W^T tensors were rewritten in
+    # place (no version bump): publishing one drops what was derived from the old
+    _COPIES.drop_pinned()
+    for w, wt, sp in zip(plan.tr_weights, plan.wts, sig):
+        _COPIES.publish(w, step_state.WT, wt, (sp != 0, w.shape))
+    for f in plan.frag:
+        co, ci = f.weight.shape[:2]
+        if f.kind == "fwd":         # forward: keyed by the parameter; data gradient: by the W^T tensor _conv_fwd is handed
+            _COPIES.publish(f.weight, step_state.FRAG, f.copy, (co, ci))
+        else:
+            _COPIES.publish(plan.wts[f.tr_index], step_state.FRAG, f.copy, (ci, co), with_source=True)
+    plan.wt_made = (_COPIES.epoch, versions)
+    plan.wt_serial += 1
+
+
+def _refresh_lowp(plan):
+    """16-bit copies of every layer's weight and W^T for this step: one multi-tensor copy (per-layer .to() calls were
+    ~190 launches / 0.8 ms of the bf16 step)."""
+    made = (_COPIES.epoch, plan.wt_serial, tuple(t._version for t in plan.lowp_srcs))
+    if plan.lowp_made == made:
+        return
+    # memory order of a channels-last parameter IS the tap-major [Cout][R][S][Cin] order the kernels read
+    flat = [t.permute(0, 2, 3, 1).reshape(-1) if (t.dim() == 4 and not t.is_contiguous()) else t.reshape(-1)
+            for t in plan.lowp_srcs]
+    torch._foreach_copy_(plan.lowp_dsts, flat)
+    dtype, weights = _LOWP[plan.precision][1], len(plan.lowp_srcs) - len(plan.wts)
+    for i, (t, d) in enumerate(zip(plan.lowp_srcs, plan.lowp_dsts)):
+        _COPIES.publish(t, step_state.LOWP, d, (dtype, t.numel()), with_source=i >= weights)
+    plan.lowp_made = made
 
 
 def prepare_step(model):
@@ -840,6 +968,7 @@ def _prepare_step(model, grad_on):
         logical shape and state-dict contents), which is the forward kernel's layout and the layout the
         weight-gradient kernel writes -- no per-call re-layout, no layout-contract clone in AccumulateGrad;
       * W^T [Cin][R][S][Cout] of every stride-1 layer for the data-gradient kernel, all layers in ONE launch;
+      * in a 16-bit precision: 16-bit copies of the weights and of their W^T;
       * when gradients are enabled: one zero-filled arena with a slot per weight gradient and per BatchNorm's
         (d shift, d gamma, d conv-bias) sums, so that the ~300 per-layer fills of a backward pass become one.
     """
@@ -851,153 +980,21 @@ def _prepare_step(model, grad_on):
         # leftovers of a backward pass that raised before its end-of-pass callback ran: their slots are about to be cleared
         _WGQ["queues"].clear()
         _WGQ["armed"] = False
-    if len(_WB) > 4096:
-        # bf16 copies of weights that were temporaries (the deconv's reshaped weight, transposes made on the fly)
-        # keep their source alive; inference loops never bump a parameter version, so bound the cache here
-        _WB.clear()
-    plan = _PLAN.get(model)
-    ptrs = tuple(p.data_ptr() for p in model.parameters())
-    if plan is None or plan["ptrs"] != ptrs or plan["layout"].superseded:
-        if plan is not None:
-            for k in plan.get("wf_keys", ()):          # the replaced plan's fragment-major copies
-                _WF.pop(k, None)
-        for cache in (_WT, _WF):                       # entries of models that no longer exist (W^T first: it owns the
-                                                       # tensors the data-gradient entries of _WF are keyed by)
-            for k in [k for k, e in cache.items() if e[3]() is None]:
-                del cache[k]
-        convs = [m for m in model.modules() if isinstance(m, Conv2d) and not m.full_window]
-        for m in convs:
-            w = m.weight
-            if w.shape[1] % 16 == 0 and w.shape[2] * w.shape[3] > 1 and \
-                    not w.is_contiguous(memory_format=torch.channels_last):
-                w.data = w.data.contiguous(memory_format=torch.channels_last)
-        tr = [m for m in convs if (tuple(m.stride) == (1, 1) or m.weight.shape[2] * m.weight.shape[3] == 1) and
-              m.weight.shape[0] % 16 == 0 and
-              m.weight.shape[1] % 16 == 0 and m.weight.shape[2] * m.weight.shape[3] <= 64 and m.weight.requires_grad]
-        desc = np.zeros(len(tr), dtype=_TR_DESC)
-        wts, base = [], 0
-        for i, m in enumerate(tr):
-            co, ci, r, s_ = m.weight.shape
-            wt = torch.empty((ci, r, s_, co), device=dev, dtype=torch.float32)
-            wts.append(wt)
-            desc[i] = (m.weight.data_ptr(), wt.data_ptr(), co, ci, r * s_, 0, base, 0)
-            base += r * s_ * ((co + 31) // 32) * ((ci + 31) // 32)
-        # fragment-major copies of the 1x1 / stride-1 weights for the persistent 1x1 kernel (conv1x1_ring_kernel,
-        # weight_layout 3): W itself for the forward pass, W^T (with the eval-BatchNorm scale, like the plain W^T) for the
-        # data gradient -- extra descriptors of the SAME launch (flag 1 = fragment-major, flag 2 = no transpose)
-        frag = []           # (module, "fwd" | "dgrad", tensor, index of the module in tr or -1)
-        tr_index = {m: i for i, m in enumerate(tr)}
-        for m in convs:
-            co, ci, r, s_ = m.weight.shape
-            if r * s_ != 1 or tuple(m.stride) != (1, 1) or tuple(m.padding) != (0, 0) or _PRECISION in _LOWP:
-                continue
-            if co % 128 == 0 and ci % 32 == 0 and ci >= 128:
-                frag.append((m, "fwd", torch.empty(co * ci, device=dev, dtype=torch.float32), -1))
-            if m in tr_index and ci % 128 == 0 and co % 32 == 0 and co >= 128:
-                frag.append((m, "dgrad", torch.empty(co * ci, device=dev, dtype=torch.float32), tr_index[m]))
-        if frag:
-            extra = np.zeros(len(frag), dtype=_TR_DESC)
-            for i, (m, kind, t, _) in enumerate(frag):
-                co, ci = m.weight.shape[0], m.weight.shape[1]
-                extra[i] = (m.weight.data_ptr(), t.data_ptr(), co, ci, 1, 3 if kind == "fwd" else 1, base, 0)
-                base += ((co + 31) // 32) * ((ci + 31) // 32)
-            desc = np.concatenate([desc, extra])
-        table = torch.from_numpy(desc.view(np.uint8).copy()).to(dev) if len(desc) else None
-        # gradient slots: the model-wide arena layout (grad_arena.py) -- every trainable parameter has one, in
-        # bucket order; the kernels' keys are the weight's / the BatchNorm gamma's address
-        layout = grad_arena.get_layout(model)
-        slots = {}
-        for m in convs:
-            if m.weight.requires_grad and m.weight in layout.slot:
-                slots[("dw", m.weight.data_ptr())] = layout.slot[m.weight] + (weakref.ref(m.weight),)
-            if m.bias is not None and m.bias.requires_grad and m.bias in layout.slot:
-                slots[("db", m.bias.data_ptr())] = layout.slot[m.bias] + (weakref.ref(m.bias),)
-        for bn in [m for m in model.modules() if isinstance(m, nn.BatchNorm2d)]:
-            if bn in layout.bn_slot:
-                # (4th entry: the address of the convolution bias the layout paired with this BatchNorm -- by adjacency
-                # among a module's children; a caller that combines the BatchNorm with ANOTHER convolution must not
-                # have that one's bias gradient adopted as a view of this block)
-                partner = layout.bn_partner.get(bn)
-                slots[("bn", bn.weight.data_ptr())] = (layout.bn_slot[bn], 3 * bn.num_features, weakref.ref(bn.weight),
-                                                       partner.data_ptr() if partner is not None else 0)
-        plan = {"ptrs": tuple(p.data_ptr() for p in model.parameters()), "tr": tr, "wts": wts, "table": table, "frag": frag,
-                "desc": desc, "tiles": base, "slots": slots, "layout": layout, "versions": None, "convs": convs,
-                "scales": None}
-        _PLAN[model] = plan
-    # fp32 training: W^T of a layer that is followed by an eval-mode BatchNorm carries the BatchNorm's scale
-    # (_ConvBnActFn.backward feeds the data-gradient kernel the unscaled masked gradient); the 16-bit kernels keep the
-    # plain W^T.  The pairs are known after the first forward pass (conv_bn_act registers them).
-    scales = [None] * len(plan["tr"])
-    if grad_on and _FOLD_PAIRS and plan["table"] is not None:
-        by_conv = {c: b for b, c in _FOLD_PAIRS.items()}
-        for i, m in enumerate(plan["tr"]):
-            b = by_conv.get(m)
-            if b is not None and not b.training and getattr(b, "_fi_fold", None) is not None:
-                scales[i] = b
-    sig = tuple(0 if b is None else b._fi_fold[0].data_ptr() for b in scales)
-    sig = sig + tuple(sig[ti] if ti >= 0 else 0 for _, _, _, ti in plan["frag"])
-    if plan["table"] is not None and plan["scales"] != sig:
-        desc = plan["desc"]
-        desc["row_scale"] = sig
-        plan["table"] = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
-        plan["scales"] = sig
-        plan["versions"] = None
-    versions = tuple(m.weight._version for m in plan["tr"]) + tuple(b._fi_fold[2] for b in scales if b is not None)
-    versions = versions + tuple(m.weight._version for m, _, _, ti in plan["frag"] if ti < 0)
-    if plan["table"] is not None and (plan["versions"] != versions or not all(
-            _cached_wt(m.weight, sig[0] != 0) is not None for m in plan["tr"][:1])):
-        L = _lib.load()
-        with torch.cuda.device(dev):
-            _lib.check(L.fi_weight_transpose_batch(_lib.ptr(plan["table"]), len(plan["desc"]), plan["tiles"],
-                                                   _lib.current_stream()), "fi_weight_transpose_batch")
-        for m, wt, sp in zip(plan["tr"], plan["wts"], sig):
-            _WT[m.weight.data_ptr()] = (wt, m.weight._version, sp != 0, weakref.ref(m.weight))
-        keys = []
-        for m, kind, t, ti in plan["frag"]:
-            # forward: keyed by the parameter; data gradient: keyed by the W^T tensor _conv_fwd is handed
-            if kind == "fwd":
-                keys.append(m.weight.data_ptr())
-                _WF[keys[-1]] = (t, m.weight._version, tuple(m.weight.shape[:2]), weakref.ref(m.weight))
-            else:
-                keys.append(plan["wts"][ti].data_ptr())
-                _WF[keys[-1]] = (t, None, (m.weight.shape[1], m.weight.shape[0]), weakref.ref(plan["wts"][ti]))
-        plan["wf_keys"] = keys
-        plan["versions"] = versions
-        _WB.clear()          # the W^T tensors were rewritten in place (no version bump): drop their bf16 copies
-    if _PRECISION in _LOWP:
-        # 16-bit copies of every layer's weight and W^T for this step: one multi-tensor copy (per-layer .to() calls were
-        # ~190 launches / 0.8 ms of the bf16 step)
-        dtype = _LOWP[_PRECISION][1]
-        lw = plan.get("lowp")
-        if lw is None or lw["dtype"] != dtype:
-            srcs = [m.weight for m in plan["convs"] if m.weight.shape[1] % 32 == 0] + list(plan["wts"])
-            lw = plan["lowp"] = {"dtype": dtype, "srcs": srcs, "versions": None,
-                                 "dsts": [torch.empty(t.numel(), device=dev, dtype=dtype) for t in srcs]}
-        vers = tuple(t._version for t in lw["srcs"]) + (plan["versions"],)
-        stale = lw["versions"] != vers or any(_WB.get(t.data_ptr(), (None,))[0] is not d
-                                               for t, d in zip(lw["srcs"][:1], lw["dsts"][:1]))
-        if stale and lw["srcs"]:
-            # memory order of a channels-last parameter IS the tap-major [Cout][R][S][Cin] order the kernels read
-            flat = [t.permute(0, 2, 3, 1).reshape(-1) if (t.dim() == 4 and not t.is_contiguous()) else t.reshape(-1)
-                    for t in lw["srcs"]]
-            torch._foreach_copy_(lw["dsts"], flat)
-            for t, d in zip(lw["srcs"], lw["dsts"]):
-                _WB[t.data_ptr()] = (d, t._version, tuple(t.shape), t)
-            lw["versions"] = vers
-    layout = plan["layout"]
+    _COPIES.bound()
+    plan = _plan_for(model, dev)
+    if plan.table is not None:
+        _refresh_transposes(plan, grad_on, dev)
+    if plan.lowp_srcs:
+        _refresh_lowp(plan)
+    layout = plan.layout
     if grad_on and layout.total:
-        buf = layout.buffer(dev)
-        if layout.live_gradients(buf):
-            # gradients of an earlier backward pass are still attached (accumulation without zero_grad): they live
-            # in the arena, so it cannot be cleared -- this pass's kernels allocate their own outputs and autograd
-            # adds them to the attached gradients
-            _ARENA["buf"] = None
-        else:
-            _ARENA["buf"] = layout.zero(dev)         # ONE fill per step, same addresses every step
-        _ARENA["slots"] = plan["slots"]
-        _ARENA["used"] = set()
+        # gradients of an earlier backward pass still attached (accumulation without zero_grad) live in the arena, so it
+        # cannot be cleared: this pass's kernels allocate their own outputs and autograd adds them to the attached ones.
+        # Otherwise ONE fill per step, same addresses every step
+        live = layout.live_gradients(layout.buffer(dev))
+        _GRADS.arm(plan.slots, None if live else layout.zero(dev))
     else:
-        _ARENA["buf"] = None
+        _GRADS.disarm()
 
 
 _UNSCALED_BACKWARD = not os.environ.get("FI_BN_BWD_OLD")      # A/B switch (scripts/ab_env.sh)
@@ -1101,7 +1098,7 @@ class _ConvBnActFn(torch.autograd.Function):
         N, C, OH, OW = y.shape
         if not ctx.needs_input_grad[1]:
             return None                          # frozen weights: no weight gradient to take the sums from
-        sums, first = _arena_take(("bn", gamma.data_ptr()), 3 * C, partner=b.data_ptr() if has_bias else 0)
+        sums, first = _GRADS.take(("bn", gamma.data_ptr()), 3 * C, partner=b.data_ptr() if has_bias else 0)
         if sums is not None and not first:
             return None                          # applied more than once this step: sums and dW accumulate
         L = _lib.load()
@@ -1163,7 +1160,7 @@ class _ConvBnActFn(torch.autograd.Function):
         dz = torch.empty(y.shape, device=y.device, dtype=torch.float32)
         g_res = torch.empty_like(y) if (has_res and ctx.needs_input_grad[8]) else None
         # (d shift, d gamma, d conv-bias) adjacent: a slot of the step's zeroed arena, or ONE fill in the call
-        sums, first = _arena_take(("bn", gamma.data_ptr()), 3 * C, partner=b.data_ptr() if has_bias else 0)
+        sums, first = _GRADS.take(("bn", gamma.data_ptr()), 3 * C, partner=b.data_ptr() if has_bias else 0)
         flags = _lib.OUTPUTS_ZEROED if sums is not None else 0
         if sums is None:
             sums, first = torch.empty(3 * C, device=y.device, dtype=torch.float32), True
@@ -1236,7 +1233,7 @@ class _ConvBiasActFn(torch.autograd.Function):
         dz = torch.empty_like(y)
         ones = _ones(C, y.device)
         # the bias gradient accumulates in the bias's arena slot (a layer applied on 5 pyramid levels: one slot)
-        dshift, first = _arena_take(("db", ctx.bias_ptr), C) if ctx.bias_ptr else (None, False)
+        dshift, first = _GRADS.take(("db", ctx.bias_ptr), C) if ctx.bias_ptr else (None, False)
         flags = _lib.OUTPUTS_ZEROED if dshift is not None else 0
         if dshift is None:
             dshift, first = torch.empty(C, device=y.device, dtype=torch.float32), True

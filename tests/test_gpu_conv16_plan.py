@@ -128,19 +128,19 @@ def test_conv_fwd_converts_a_temporary_only_where_the_plan_reads_the_copy(sfx):
     C.invalidate_step_state()
     try:
         C._cached_bf16(w, DTYPES[sfx])                       # as _prepare_step leaves a model weight: in the cache
-        assert len(C._WB) == 1
+        assert len(C._COPIES.having("lowp")) == 1
         y_cached = C._conv_fwd(x, w, None, (1, 1), (0, 0), precision=PRECISION[sfx])
-        assert len(C._WB) == 1
+        assert len(C._COPIES.having("lowp")) == 1
         fresh = w.clone()
         y_fresh = C._conv_fwd(x, fresh, None, (1, 1), (0, 0), precision=PRECISION[sfx])
         torch.cuda.synchronize()
-        assert len(C._WB) == 2 and fresh.data_ptr() in C._WB
+        assert len(C._COPIES.having("lowp")) == 2 and fresh.data_ptr() in C._COPIES.table
         assert torch.equal(y_cached, y_fresh)
         R.check_bar(y_fresh, ref, mag, Cin, "reg1x1 through _conv_fwd")
         xn, wn, refn, magn = _problem("reg1x1_nb", sfx)
         yn = C._conv_fwd(xn, wn.view(Cout, Cin, 1, 1).clone(), None, (1, 1), (0, 0), precision=PRECISION[sfx])
         torch.cuda.synchronize()
-        assert len(C._WB) == 2                               # the generic kernel reads the fp32 weights: nothing converted
+        assert len(C._COPIES.having("lowp")) == 2                # the generic kernel reads the fp32 weights: nothing converted
         R.check_bar(yn, refn, magn, Cin, "reg1x1_nb through _conv_fwd")
     finally:
         C.invalidate_step_state()
@@ -162,7 +162,7 @@ def test_conv_fwd_with_a_misaligned_x_takes_the_generic_kernel(sfx):
     try:
         got = C._conv_fwd(xm, w, None, (1, 1), (1, 1), w_tap_major=True, precision=PRECISION[sfx])
         torch.cuda.synchronize()
-        assert len(C._WB) == 0
+        assert len(C._COPIES.having("lowp")) == 0
     finally:
         C.invalidate_step_state()
     R.check_bar(got, ref, mag, Cin * 9, "3x3 with x at a 4-byte offset")

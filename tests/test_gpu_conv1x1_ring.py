@@ -137,9 +137,10 @@ def test_model_layers_take_the_ring_kernel_and_match_the_reg_kernel(monkeypatch)
         C.invalidate_step_state()
         xx = step()
         if ring:
-            assert len(C._WF) == 4          # two layers x (forward, data gradient)
+            assert len(C._COPIES.having("frag")) == 4          # two layers x (forward, data gradient)
         else:
-            C._WF.clear()
+            for _, rec in C._COPIES.having("frag"):
+                del rec.copies["frag"]
         y = net(xx)
         (y * torch.linspace(0.5, 1.5, y.numel(), device=DEV).view_as(y)).sum().backward()
         torch.cuda.synchronize()
@@ -170,7 +171,7 @@ def test_a_collected_models_fragment_copies_are_not_used_for_the_next_model():
     C.prepare_step(a)
     torch.cuda.synchronize()
     key = a.conv.weight.data_ptr()
-    assert key in C._WF
+    assert "frag" in C._COPIES.table[key].copies
     del a
     gc.collect()
     # a tensor of the same shape at the freed address, not a parameter of any planned model
@@ -182,14 +183,15 @@ def test_a_collected_models_fragment_copies_are_not_used_for_the_next_model():
             break
     if w is None:
         pytest.skip("the allocator did not hand the freed block back")
-    assert C._WF[key][3]() is None                      # the owner is gone
-    while w._version < C._WF[key][1]:
+    rec = C._COPIES.table[key]
+    assert rec.owner() is None and "frag" in rec.copies  # the owner is gone
+    while w._version < rec.version:
         w.add_(0)                                       # (a parameter's counter after its initialisation)
-    assert C._WF[key][1] == w._version                  # version / shape alone would have matched
+    assert rec.version == w._version                    # version / shape alone would have matched
     y = C._conv_fwd(x, w, None, (1, 1), (0, 0))
     ref = torch.nn.functional.conv2d(x.double(), w.double()).float()
     assert torch.allclose(y, ref, rtol=1e-4, atol=1e-3)
     b = One().to(DEV)
     C.prepare_step(b)                                   # a new plan sweeps the dead entries
-    assert all(e[3]() is not None for e in C._WF.values())
+    assert all(r.owner() is not None for r in C._COPIES.table.values())
     C.invalidate_step_state()
