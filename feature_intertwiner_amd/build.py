@@ -37,6 +37,11 @@ OT_HEADERS = SINKHORN_HEADERS + [os.path.join("..", "..", "include", "fi_ot.h")]
 CONVT_LIB_PATH = os.path.join(_HERE, "libfi_convt.so")
 CONVT_SOURCES = ["conv_transpose.hip"]
 CONVT_HEADERS = [os.path.join("..", "..", "include", "fi_convt.h")]
+# convolutions on 16-bit channels-last activation tensors and the casts at their boundary (include/fi_act16.h): a seventh
+# library, built the same way
+ACT16_LIB_PATH = os.path.join(_HERE, "libfi_act16.so")
+ACT16_SOURCES = ["conv_act16.hip", "conv_act16_f16.hip"]
+ACT16_HEADERS = [os.path.join("..", "..", "include", "fi_act16.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
@@ -66,6 +71,7 @@ def _compile(sources, headers, force, verbose):
         o = s[:-4] + ".o"
         deps = [s] + hdrs + ([os.path.join(CSRC, "conv_bf16.hip")] if s.endswith("conv_f16.hip") else [])
         deps += [os.path.join(CSRC, h) for h in SINKHORN_HEADERS] if s.endswith("sinkhorn.hip") else []
+        deps += [os.path.join(CSRC, "conv_act16.hip")] if s.endswith("conv_act16_f16.hip") else []
         if force or _stale(o, deps):
             cmd = [HIPCC] + FLAGS + ["-c", s, "-o", o]
             if verbose:
@@ -76,8 +82,8 @@ def _compile(sources, headers, force, verbose):
 
 
 def build_hip(force=False, verbose=False):
-    """Builds libfi_hip.so, libfi_eval.so, libfi_cocoeval.so, libfi_cocomask.so, libfi_ot.so and libfi_convt.so; returns the
-    path of the first."""
+    """Builds libfi_hip.so, libfi_eval.so, libfi_cocoeval.so, libfi_cocomask.so, libfi_ot.so, libfi_convt.so and
+    libfi_act16.so; returns the path of the first."""
     objs = _compile(SOURCES, HEADERS, force, verbose)
     if force or _stale(LIB_PATH, objs):
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
@@ -88,7 +94,8 @@ def build_hip(force=False, verbose=False):
                                   (COCOEVAL_LIB_PATH, COCOEVAL_SOURCES, COCOEVAL_HEADERS),
                                   (COCOMASK_LIB_PATH, COCOMASK_SOURCES, COCOMASK_HEADERS),
                                   (OT_LIB_PATH, OT_SOURCES, OT_HEADERS),
-                                  (CONVT_LIB_PATH, CONVT_SOURCES, CONVT_HEADERS)):
+                                  (CONVT_LIB_PATH, CONVT_SOURCES, CONVT_HEADERS),
+                                  (ACT16_LIB_PATH, ACT16_SOURCES, ACT16_HEADERS)):
         objs = _compile(sources, HEADERS + headers, force, verbose)
         if force or _stale(lib, objs + [LIB_PATH]):
             cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + [

@@ -103,6 +103,9 @@ class MaskRCNN(nn.Module):
         bs = images.size(0)
         if mode == 'inference':
             return self._inference(images, input[1])
+        if getattr(cfg.MODEL, "ACT_PRECISION", "fp32") != "fp32":
+            raise NotImplementedError("MODEL.ACT_PRECISION = %r: training on 16-bit activation tensors is not built "
+                                      "(the 16-bit trunk is forward only: mode='inference')" % (cfg.MODEL.ACT_PRECISION,))
         gt_class_ids, gt_boxes, gt_masks = input[1], input[2], input[3]
         self.eval()   # the reference always runs BN (and everything else) in eval mode
         join, self._side_join = getattr(self, "_side_join", None), None

@@ -16,6 +16,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from . import act16 as _act16
 from . import conv as _conv
 from .conv import (Conv2d, ConvTranspose2x2, ConvTranspose3x3, GradBox, conv1x1_class_rows, conv2d, conv_bias_relu,
                    conv_bn_act, convt_bn_act, linear, maxpool3x3s2, take_rows, upsample2x)
@@ -113,6 +114,15 @@ class Bottleneck(nn.Module):
         self.lateral_box = None       # set for ONE forward call by FPN.forward on the first block of C3..C5
 
     def forward(self, x):
+        if _act16.is_act16(x):
+            # a 16-bit channels-last map (MODEL.ACT_PRECISION, inference): every layer reads and writes one, the shortcut
+            # is added in conv3's epilogue
+            out = _act16.conv_bn_act16(x, self.conv1, self.bn1, relu=True)
+            out = _act16.conv_bn_act16(out, self.conv2, self.bn2, relu=True)
+            residual = x
+            if self.downsample is not None:
+                residual = _act16.conv_bn_act16(x, self.downsample[0], self.downsample[1], relu=False)
+            return _act16.conv_bn_act16(out, self.conv3, self.bn3, relu=True, residual=residual)
         # conv + eval-BN (+ shortcut) + ReLU are one kernel launch each (conv.conv_bn_act)
         if self.downsample is None and _fused_path(x, self.bn1, self.bn3) and x.requires_grad and torch.is_grad_enabled():
             # identity shortcut: x receives two gradients, conv1's data gradient and the shortcut's.  The
@@ -222,8 +232,18 @@ class FPN(nn.Module):
     def forward(self, x, mode='train'):
         bs = x.size(0)
         ot_loss = x.new_zeros(bs, 3)
+        # MODEL.ACT_PRECISION 'bf16' / 'fp16': the trunk C2..C5 on 16-bit channels-last tensors -- inference only
+        act = getattr(self.config.MODEL, "ACT_PRECISION", "fp32")
+        if act != "fp32":
+            act_dtype = _act16.dtype_of(act)
+            if mode == 'train':
+                raise NotImplementedError("MODEL.ACT_PRECISION = %r: training on 16-bit activation tensors is not built "
+                                          "(the 16-bit trunk is forward only: mode='inference')" % (act,))
+        act = act != "fp32" and mode == 'inference' and x.is_cuda and not torch.is_grad_enabled()
         x = conv_bn_act(x, self.C1[0], self.C1[1], relu=True)       # C1 = conv, bn, relu, pad, maxpool
         x = _pad_maxpool(x, self.C1[3], self.C1[4])
+        if act:
+            x = _act16.pack(x, act_dtype)       # the pooled map, once; c2..c5 leave as fp32 NCHW (four launches)
         # c2..c4 are read by the next stage AND by their lateral convolution: the lateral hands its data gradient to the
         # next stage's first block (GradBox; see Bottleneck.forward), which is the only one left talking to autograd
         fuse = mode == 'train' and not self.ot and x.is_cuda and torch.is_grad_enabled() and _conv.GATES
@@ -237,6 +257,9 @@ class FPN(nn.Module):
             c[lvl] = stage(c[lvl - 1])
             if first is not None:
                 first.lateral_box = None           # not picked up (the block took another path): nothing is given
+        if act:
+            c = {lvl: _act16.unpack(m) for lvl, m in c.items()}
+            c2 = c[2]
         c3, c4, c5 = c[3], c[4], c[5]
         p5 = self.P5_conv1(c5)
         up = upsample2x
