@@ -127,6 +127,26 @@ def conv_bn_act16(x16, conv, bn, relu=True, residual=None):
                            "tensors is not built)")
     if bn.training or not bn.track_running_stats:
         raise _lib.FiError("conv_bn_act16 folds an eval-mode BatchNorm with running statistics; got one in training mode")
+    _conv._FOLD_PAIRS[bn] = conv
+    fold = _conv._cached_fold(conv, bn)
+    if fold is None:
+        _conv.refresh_bn_folds()
+        fold = _conv._cached_fold(conv, bn)
+    return _conv16("conv_bn_act16", x16, prec, conv, fold[0], fold[1], relu, residual)
+
+
+def weight16(weight, dtype):
+    """The tap-major [Cout, R, S, Cin] 16-bit copy of a [Cout, Cin, R, S] weight: a view of a channels-last (or 1x1)
+    weight goes through conv's registry; a 3x3 weight still stored [Cout, Cin, R, S] (no prepare_step yet) is converted
+    for this call and not registered -- the registry would pin one tap-major temporary per call."""
+    wt = weight.permute(0, 2, 3, 1)                 # (no graph: grad mode is off)
+    if wt.is_contiguous():
+        return _conv._cached_bf16(wt, dtype)
+    return wt.to(dtype).contiguous()
+
+
+def _conv16(what, x16, prec, conv, scale, shift, relu, residual):
+    """One fi_act16_conv_forward launch of `conv` on x16 with the fp32 per-channel scale / shift (each may be None)."""
     L = load()
     dtype = x16.dtype
     N, Cin, H, W = x16.shape
@@ -134,35 +154,22 @@ def conv_bn_act16(x16, conv, bn, relu=True, residual=None):
     stride, pad = conv.stride, conv.padding
     if stride[0] != stride[1] or pad[0] != pad[1] or tuple(conv.dilation) != (1, 1) or conv.groups != 1 or \
             conv.weight.shape[1] != Cin:
-        raise _lib.FiError("conv_bn_act16: the layer must be a dense square-stride convolution of the input's %d channels "
+        raise _lib.FiError(what + ": the layer must be a dense square-stride convolution of the input's %d channels "
                            "(stride %s, padding %s, dilation %s, groups %d, weight %s)"
                            % (Cin, tuple(stride), tuple(pad), tuple(conv.dilation), conv.groups, tuple(conv.weight.shape)))
     OH = (H + 2 * pad[0] - R) // stride[0] + 1
     OW = (W + 2 * pad[1] - S) // stride[1] + 1
     if residual is not None:
-        _require_act16(residual, "conv_bn_act16 (residual)")
+        _require_act16(residual, what + " (residual)")
         if residual.dtype != dtype or tuple(residual.shape) != (N, Cout, OH, OW):
-            raise _lib.FiError("conv_bn_act16: residual %s %s does not match the output %s %s"
-                               % (residual.dtype, tuple(residual.shape), dtype, (N, Cout, OH, OW)))
-    _conv._FOLD_PAIRS[bn] = conv
-    fold = _conv._cached_fold(conv, bn)
-    if fold is None:
-        _conv.refresh_bn_folds()
-        fold = _conv._cached_fold(conv, bn)
-    scale, shift = fold
-    # the tap-major [Cout, R, S, Cin] weight (a view of a channels-last parameter) and its 16-bit copy in conv's registry
-    wt = conv.weight.permute(0, 2, 3, 1)            # (no graph: grad mode is off)
-    if wt.is_contiguous():
-        w16 = _conv._cached_bf16(wt, dtype)
-    else:
-        # a 3x3 weight still stored [Cout, Cin, R, S] (no prepare_step yet): converted for this call and not registered --
-        # the registry would pin one tap-major temporary per call
-        w16 = wt.to(dtype).contiguous()
+            raise _lib.FiError("%s: residual %s %s does not match the output %s %s"
+                               % (what, residual.dtype, tuple(residual.shape), dtype, (N, Cout, OH, OW)))
+    w16 = weight16(conv.weight, dtype)
     y = torch.empty((N, Cout, max(OH, 0), max(OW, 0)), device=x16.device, dtype=dtype, memory_format=torch.channels_last)
     args = (N, H, W, Cin, Cout, R, S, stride[0], pad[0])
     if N > 0 and L.fi_act16_conv_eligible(*args, _lib.ptr(x16), _lib.ptr(w16), _lib.ptr(residual), _lib.ptr(y)) != 1:
-        raise _lib.FiError("conv_bn_act16: fi_act16_conv_eligible refuses this layer (N %d, H %d, W %d, Cin %d, Cout %d, "
-                           "R %d, S %d, stride %d, pad %d); there is no fallback" % args)
+        raise _lib.FiError("%s: fi_act16_conv_eligible refuses this layer (N %%d, H %%d, W %%d, Cin %%d, Cout %%d, "
+                           "R %%d, S %%d, stride %%d, pad %%d); there is no fallback" % what % args)
     _launch(x16.device, "fi_act16_conv_forward", _conv._lowp_fn(L, "act16_conv_forward", prec), _lib.ptr(x16),
             _lib.ptr(w16), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual), _lib.ptr(y), *args, 1 if relu else 0)
     _STATS["conv"] += 1

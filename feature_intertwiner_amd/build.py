@@ -41,7 +41,14 @@ CONVT_HEADERS = [os.path.join("..", "..", "include", "fi_convt.h")]
 # library, built the same way
 ACT16_LIB_PATH = os.path.join(_HERE, "libfi_act16.so")
 ACT16_SOURCES = ["conv_act16.hip", "conv_act16_f16.hip"]
-ACT16_HEADERS = [os.path.join("..", "..", "include", "fi_act16.h")]
+# device code that conv_act16.hip (libfi_act16.so) and conv_pyr16.hip (libfi_pyr16.so) share
+ACT16_DEV_HEADERS = ["conv_act16_dev.h"]
+ACT16_HEADERS = ACT16_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_act16.h")]
+# the pyramid's lateral step and the RPN's stacked heads on 16-bit channels-last tensors (include/fi_pyr16.h): an eighth
+# library, built the same way
+PYR16_LIB_PATH = os.path.join(_HERE, "libfi_pyr16.so")
+PYR16_SOURCES = ["conv_pyr16.hip", "conv_pyr16_f16.hip"]
+PYR16_HEADERS = ACT16_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_pyr16.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
@@ -72,6 +79,7 @@ def _compile(sources, headers, force, verbose):
         deps = [s] + hdrs + ([os.path.join(CSRC, "conv_bf16.hip")] if s.endswith("conv_f16.hip") else [])
         deps += [os.path.join(CSRC, h) for h in SINKHORN_HEADERS] if s.endswith("sinkhorn.hip") else []
         deps += [os.path.join(CSRC, "conv_act16.hip")] if s.endswith("conv_act16_f16.hip") else []
+        deps += [os.path.join(CSRC, "conv_pyr16.hip")] if s.endswith("conv_pyr16_f16.hip") else []
         if force or _stale(o, deps):
             cmd = [HIPCC] + FLAGS + ["-c", s, "-o", o]
             if verbose:
@@ -82,8 +90,8 @@ def _compile(sources, headers, force, verbose):
 
 
 def build_hip(force=False, verbose=False):
-    """Builds libfi_hip.so, libfi_eval.so, libfi_cocoeval.so, libfi_cocomask.so, libfi_ot.so, libfi_convt.so and
-    libfi_act16.so; returns the path of the first."""
+    """Builds libfi_hip.so, libfi_eval.so, libfi_cocoeval.so, libfi_cocomask.so, libfi_ot.so, libfi_convt.so,
+    libfi_act16.so and libfi_pyr16.so; returns the path of the first."""
     objs = _compile(SOURCES, HEADERS, force, verbose)
     if force or _stale(LIB_PATH, objs):
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
@@ -95,7 +103,8 @@ def build_hip(force=False, verbose=False):
                                   (COCOMASK_LIB_PATH, COCOMASK_SOURCES, COCOMASK_HEADERS),
                                   (OT_LIB_PATH, OT_SOURCES, OT_HEADERS),
                                   (CONVT_LIB_PATH, CONVT_SOURCES, CONVT_HEADERS),
-                                  (ACT16_LIB_PATH, ACT16_SOURCES, ACT16_HEADERS)):
+                                  (ACT16_LIB_PATH, ACT16_SOURCES, ACT16_HEADERS),
+                                  (PYR16_LIB_PATH, PYR16_SOURCES, PYR16_HEADERS)):
         objs = _compile(sources, HEADERS + headers, force, verbose)
         if force or _stale(lib, objs + [LIB_PATH]):
             cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + [

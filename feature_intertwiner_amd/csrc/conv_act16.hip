@@ -2,21 +2,7 @@
 // (v_mfma_f32_32x32x16_bf16, fp32 accumulation) and the transposing casts at the boundary to fp32 NCHW.
 // conv_act16_f16.hip includes this file with FI_E16_HALF defined: the same kernels on IEEE half under the *_f16 names.
 //
-// Orientation.  D[m][p] = sum_k A[m][k] B[k][p] with m = output channel, p = output pixel flattened over N*OH*OW (a pixel
-// tile may span images) and k = (tap, input channel).  In NHWC with tap-major weights BOTH operands are contiguous along
-// k: a weight row w[m][tap][ci..] and an activation row x[pixel of the tap][ci..].  A lane's MFMA fragment -- A[row][8h+j],
-// B[8h+j][col], j = 0..7 -- is therefore ONE 16-byte chunk of such a row: global -> LDS is 16-byte loads and 16-byte LDS
-// writes with no conversion and no transposing write, LDS -> registers one 16-byte read per fragment.
-// LDS.  A tile row holds BK 16-bit values = CPR chunks of 16 bytes.  Chunk c of row r is stored at chunk position
-// c ^ ((r / (16 / CPR)) % CPR): the 16 lanes the hardware serves together read 16 consecutive rows at one chunk index,
-// and with the XOR they fall on 16 different 16-byte slots of the 256-byte bank row (no conflict); the writes of a row's
-// chunks by neighbouring lanes stay inside that row's bytes (no conflict either).
-// Pipeline.  Register staging with two LDS buffers: the loads of K block i+1 are issued before the MFMAs of block i and
-// written to the other buffer after them; one barrier per K block.  K blocks run taps outer (row-major), channels inner:
-// one fixed summation order per element whatever the grid.
-// 3x3.  The B row of tap (r, s) for output pixel (oh, ow) is input pixel (oh + r - 1, ow + s - 1); outside the map the
-// chunk is a zero selected on the way to LDS and NO address is formed.  Rows of the tile past the last pixel / channel
-// are zeros too.
+// Orientation, LDS layout, pipeline and the main loop itself: conv_act16_dev.h, which conv_pyr16.hip (libfi_pyr16.so) shares.
 // Epilogue.  C/D map col = lane & 31 (pixel), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) (channel): a register quad
 // is 4 consecutive channels of one pixel.  Stored straight from that map a wave's instruction touches 32 pixels with 16
 // bytes each (a stride of Cout * 2 bytes): the layers with Cin = 64 have ONE K block and are all epilogue, and ran at
@@ -25,41 +11,10 @@
 #include <stdint.h>
 
 #include "fi_common.h"
+#include "conv_act16_dev.h"
 #include "../../include/fi_act16.h"
 
-#ifdef FI_E16_HALF
-#define E16 _Float16
-#define MFMA16 __builtin_amdgcn_mfma_f32_32x32x16_f16
-#define FI16(stem) stem##_f16
-#else
-#define E16 __bf16
-#define MFMA16 __builtin_amdgcn_mfma_f32_32x32x16_bf16
-#define FI16(stem) stem##_bf16
-#endif
-
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef E16 e16x8 __attribute__((ext_vector_type(8)));
-typedef E16 e16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kThreads = 256;     // 4 wavefronts, 2 (channels) x 2 (pixels)
-constexpr int BN = 128;           // pixel tile
-
-struct Geom {
-    int N, H, W, Cin, Cout, RS, S, stride, pad, OH, OW;
-    int P;            // N * OH * OW
-    int mtiles;       // channel tiles (the fast index of the grid: the workgroups of one pixel tile run together)
-    int relu;
-};
-
-template <int CPR>
-__device__ __forceinline__ int lds_chunk(int row, int c)
-{
-    return row * CPR + (c ^ ((row / (16 / CPR)) & (CPR - 1)));
-}
 
 // BM: channel tile (128, or 64 for the narrow layers), BK: K block (64, or 32 when Cin % 64 != 0)
 template <int BM, int BK>
@@ -69,143 +24,18 @@ __global__ __launch_bounds__(kThreads) void act16_conv_kernel(const E16 *__restr
                                                               const E16 *__restrict__ residual, E16 *__restrict__ y,
                                                               Geom g)
 {
-    constexpr int CPR = BK / 8;                    // 16-byte chunks per tile row
-    constexpr int A_IT = BM * CPR / kThreads;      // chunks a thread stages per K block
-    constexpr int B_IT = BN * CPR / kThreads;
-    constexpr int MI = BM / 64;                    // 32 x 32 blocks per wavefront along the channels
-    constexpr int NI = 2;                          // ... and along the pixels
-    // two staging buffers per operand; the epilogue reuses the bytes for the fp32 output tile
-    constexpr int STAGE_CHUNKS = 2 * (BM + BN) * CPR, OUT_CHUNKS = BN * BM / 4;
-    __shared__ u32x4 smem[STAGE_CHUNKS > OUT_CHUNKS ? STAGE_CHUNKS : OUT_CHUNKS];
-    u32x4(*As)[BM * CPR] = reinterpret_cast<u32x4(*)[BM * CPR]>(smem);
-    u32x4(*Bs)[BN * CPR] = reinterpret_cast<u32x4(*)[BN * CPR]>(smem + 2 * BM * CPR);
+    __shared__ u32x4 smem[tile_smem_chunks<BM, BK>()];
     f32x4 *Cs = reinterpret_cast<f32x4 *>(smem);
-
     const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
     const int m0 = (int)(blockIdx.x % (unsigned)g.mtiles) * BM;
     const int n0 = (int)(blockIdx.x / (unsigned)g.mtiles) * BN;          // < P < 2^31 (host check)
+    f32x16 acc[BM / 64][2];
+    conv_main_loop<BM, BK>(x, w, g, smem, m0, n0, acc);
 
-    // what this thread stages: the same tile rows and chunk index in every K block
-    long a_off[A_IT];                              // element offset of w[m][tap 0][chunk], -1: no such channel
-#pragma unroll
-    for (int i = 0; i < A_IT; ++i) {
-        const int id = tid + i * kThreads, m = m0 + id / CPR;
-        a_off[i] = m < g.Cout ? ((long)m * g.RS * g.Cin + (id % CPR) * 8) : -1;
-    }
-    long b_img[B_IT];                              // pixel index of the image's first pixel
-    int b_ih[B_IT], b_iw[B_IT];                    // input pixel of tap (0, 0); a row past the last pixel: far outside
-#pragma unroll
-    for (int i = 0; i < B_IT; ++i) {
-        const int id = tid + i * kThreads;
-        const long p = (long)n0 + id / CPR;
-        if (p < g.P) {
-            const int img = (int)(p / ((long)g.OH * g.OW));
-            const int rem = (int)(p - (long)img * g.OH * g.OW);
-            const int oh = rem / g.OW, ow = rem - oh * g.OW;
-            b_img[i] = (long)img * g.H * g.W;
-            b_ih[i] = oh * g.stride - g.pad;
-            b_iw[i] = ow * g.stride - g.pad;
-        } else {
-            b_img[i] = 0;
-            b_ih[i] = -(1 << 30);
-            b_iw[i] = -(1 << 30);
-        }
-    }
-
-    const int kblocks = g.Cin / BK;
-    const int iters = g.RS * kblocks;
-    u32x4 ra[A_IT], rb[B_IT];
-    const u32x4 zero = {0u, 0u, 0u, 0u};
-
-    auto load = [&](int it) {
-        const int tap = it / kblocks, kb = it - tap * kblocks;
-        const int r = tap / g.S, s = tap - r * g.S;
-#pragma unroll
-        for (int i = 0; i < A_IT; ++i) {
-            ra[i] = zero;
-            if (a_off[i] >= 0)
-                ra[i] = *reinterpret_cast<const u32x4 *>(w + a_off[i] + (long)tap * g.Cin + kb * BK);
-        }
-#pragma unroll
-        for (int i = 0; i < B_IT; ++i) {
-            const int ih = b_ih[i] + r, iw = b_iw[i] + s;
-            rb[i] = zero;
-            if ((unsigned)ih < (unsigned)g.H && (unsigned)iw < (unsigned)g.W) {
-                const int ch = (tid + i * kThreads) % CPR;
-                rb[i] = *reinterpret_cast<const u32x4 *>(x + (b_img[i] + (long)ih * g.W + iw) * g.Cin + kb * BK + ch * 8);
-            }
-        }
-    };
-    auto stage = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < A_IT; ++i) {
-            const int id = tid + i * kThreads;
-            As[buf][lds_chunk<CPR>(id / CPR, id % CPR)] = ra[i];
-        }
-#pragma unroll
-        for (int i = 0; i < B_IT; ++i) {
-            const int id = tid + i * kThreads;
-            Bs[buf][lds_chunk<CPR>(id / CPR, id % CPR)] = rb[i];
-        }
-    };
-
-    f32x16 acc[MI][NI];
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.f;
-
-    const int fr = lane & 31, fh = lane >> 5;      // fragment row / column, and which 8 of the 16 k
-    load(0);
-    stage(0);
-    __syncthreads();
-    for (int it = 0; it < iters; ++it) {
-        const int buf = it & 1;
-        if (it + 1 < iters) load(it + 1);
-#pragma unroll
-        for (int kk = 0; kk < BK / 16; ++kk) {
-            e16x8 a[MI], b[NI];
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-                a[mi] = *reinterpret_cast<const e16x8 *>(&As[buf][lds_chunk<CPR>(wm * (BM / 2) + mi * 32 + fr, kk * 2 + fh)]);
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni)
-                b[ni] = *reinterpret_cast<const e16x8 *>(&Bs[buf][lds_chunk<CPR>(wn * (BN / 2) + ni * 32 + fr, kk * 2 + fh)]);
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = MFMA16(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
-        }
-        if (it + 1 < iters) stage(buf ^ 1);        // last read two barriers ago
-        __syncthreads();
-    }
-
-    // epilogue.  The accumulators go through LDS (free now: the loop ends on a barrier) so that the global accesses are
-    // whole 16-byte chunks along the channels with neighbouring lanes on neighbouring chunks of one pixel: fp32 tile
-    // Cs[pixel][channel], its 16-byte chunks XORed with (pixel & 15) -- the 16 lanes served together write 16 different
-    // pixels at one channel offset and land on 16 different slots.  Then acc * scale + bias + residual, ReLU in fp32 and
-    // ONE rounding, 8 channels of one pixel per lane and store.
+    // epilogue.  The fp32 tile through LDS (tile_to_lds), then acc * scale + bias + residual, ReLU in fp32 and ONE rounding,
+    // 8 channels of one pixel per lane and store.
     constexpr int RC = BM / 4;                     // 16-byte chunks per tile row
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni) {
-        const int pr = wn * (BN / 2) + ni * 32 + fr;
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int cc = (wm * (BM / 2) + mi * 32 + 8 * q + 4 * fh) / 4;
-                f32x4 v;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = acc[mi][ni][4 * q + j];
-                Cs[pr * RC + (cc ^ (pr & 15))] = v;
-            }
-        }
-    }
-    __syncthreads();
+    tile_to_lds<BM>(acc, Cs);
     constexpr int CH8 = BM / 8;                    // 8-channel groups per tile row; kThreads % CH8 == 0: a thread keeps its group
     const int cg = tid % CH8;
     const int co = m0 + cg * 8;
@@ -314,22 +144,6 @@ __global__ __launch_bounds__(kThreads) void act16_unpack_kernel(const E16 *__res
             if (c0 + c < g.C && p0 + p < g.HW) y[(n * g.C + c0 + c) * g.HW + p0 + p] = tile[c][p];
         }
     }
-}
-
-constexpr long kIntMax = 2147483647L;
-
-constexpr long kCUs = 256;        // compute units of an MI355X
-
-// The channel tile of a launch: 64 rows where a 128-row tile would be at most half full (C2's conv1 / conv2), and where
-// 128-row tiles would give at most one workgroup per compute unit (the 3x3 layers of C4 / C5: a lone workgroup leaves every
-// SIMD with a single wavefront and nothing to hide its barrier behind).  Measured, bf16 (profiles/act16_probe.txt): 3x3
-// 256 -> 256 on 4 x 64 x 64, 256 workgroups of 128 rows 0.072 ms, 512 of 64 rows 0.064 ms; 3x3 128 -> 128 on 2 x 168 x 168,
-// 441 of 128 rows 0.060 ms, 882 of 64 rows 0.066 ms -- past one workgroup per CU the larger tile's reuse wins.
-inline int conv_bm(int Cout, long P)
-{
-    if (Cout <= 64) return 64;
-    const long blocks128 = ((P + BN - 1) / BN) * ((Cout + 127) / 128);
-    return blocks128 <= kCUs ? 64 : 128;
 }
 
 // THE statement of what the convolution takes (the pointers may be NULL: not known yet)

@@ -7,7 +7,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import act16 as _act16
 from . import conv as _conv
+from . import pyr16 as _pyr16
 import os as _os
 # the mask head's batch whose results nothing reads runs on the second stream (same-box A/B 120.3 -> 117.2 ms/step)
 _DEAD_SIDE = _os.environ.get('FI_DEAD_SIDE', '1') != '0'
@@ -32,6 +34,7 @@ class MaskRCNN(nn.Module):
     def __init__(self, config):
         super(MaskRCNN, self).__init__()
         self.config = config
+        _pyr16.act_scope(config.MODEL)      # ValueError for a MODEL.ACT_SCOPE that its MODEL.ACT_PRECISION cannot carry
         self._build(config)
         self._initialize_weights()
         self.feature_buffer = None
@@ -101,6 +104,7 @@ class MaskRCNN(nn.Module):
         cfg = self.config
         images = input[0]
         bs = images.size(0)
+        _pyr16.act_scope(cfg.MODEL)
         if mode == 'inference':
             return self._inference(images, input[1])
         if getattr(cfg.MODEL, "ACT_PRECISION", "fp32") != "fp32":
@@ -291,6 +295,9 @@ class MaskRCNN(nn.Module):
         prepare_step(self)
         p2, p3, p4, p5, p6, _ = self.fpn(images, mode='inference')
         mrcnn_maps = [p2, p3, p4, p5]
+        if _act16.is_act16(p2):
+            # MODEL.ACT_SCOPE 'pyramid': the RPN reads the 16-bit maps; the Dev stage, RoIAlign and the heads read fp32 NCHW
+            mrcnn_maps = [_act16.unpack(p) for p in mrcnn_maps]
         outs = [self.rpn(p) for p in (p2, p3, p4, p5, p6)]
         _, rpn_probs, rpn_bbox = [torch.cat(list(o), dim=1) for o in zip(*outs)]
         extra = self.external_proposals() if self.external_proposals is not None else None

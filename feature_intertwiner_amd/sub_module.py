@@ -18,6 +18,7 @@ import torch.nn.functional as F
 from . import _lib
 from . import act16 as _act16
 from . import conv as _conv
+from . import pyr16 as _pyr16
 from .conv import (Conv2d, ConvTranspose2x2, ConvTranspose3x3, GradBox, conv1x1_class_rows, conv2d, conv_bias_relu,
                    conv_bn_act, convt_bn_act, linear, maxpool3x3s2, take_rows, upsample2x)
 from .intertwiner import class_mean, roi_level
@@ -239,6 +240,7 @@ class FPN(nn.Module):
             if mode == 'train':
                 raise NotImplementedError("MODEL.ACT_PRECISION = %r: training on 16-bit activation tensors is not built "
                                           "(the 16-bit trunk is forward only: mode='inference')" % (act,))
+        scope = _pyr16.act_scope(self.config.MODEL)     # 'pyramid': p2..p6 stay 16-bit as well (_pyramid16)
         act = act != "fp32" and mode == 'inference' and x.is_cuda and not torch.is_grad_enabled()
         x = conv_bn_act(x, self.C1[0], self.C1[1], relu=True)       # C1 = conv, bn, relu, pad, maxpool
         x = _pad_maxpool(x, self.C1[3], self.C1[4])
@@ -257,6 +259,8 @@ class FPN(nn.Module):
             c[lvl] = stage(c[lvl - 1])
             if first is not None:
                 first.lateral_box = None           # not picked up (the block took another path): nothing is given
+        if act and scope == "pyramid":
+            return self._pyramid16(c) + [ot_loss]
         if act:
             c = {lvl: _act16.unpack(m) for lvl, m in c.items()}
             c2 = c[2]
@@ -287,6 +291,19 @@ class FPN(nn.Module):
         p2 = self.P2_conv2(p2)
         p6 = self.P6(p5)
         return [p2, p3, p4, p5, p6, ot_loss]
+
+    def _pyramid16(self, c):
+        """[p2 .. p6] as 16-bit channels-last tensors from the 16-bit c2..c5 (MODEL.ACT_SCOPE 'pyramid', inference): nothing
+        is unpacked, each top-down step is ONE launch that reads the coarser level at half resolution (no upsampled map),
+        the smoothing convolutions carry their folded padding, and p6 is the stride-2 subsample of p5."""
+        p5 = _pyr16.conv_bias_act16(c[5], self.P5_conv1)
+        p4 = _pyr16.lateral16(c[4], self.P4_conv1, p5)
+        p3 = _pyr16.lateral16(c[3], self.P3_conv1, p4)
+        p2 = _pyr16.lateral16(c[2], self.P2_conv1, p3)
+        p5, p4, p3, p2 = (_pyr16.conv_bias_act16(p, m[1]) for p, m in
+                          ((p5, self.P5_conv2), (p4, self.P4_conv2), (p3, self.P3_conv2), (p2, self.P2_conv2)))
+        p6 = p5[:, :, ::2, ::2].contiguous(memory_format=torch.channels_last)      # MaxPool2d(1, 2): a few KB, one copy
+        return [p2, p3, p4, p5, p6]
 
 
 class _PatchRowsFn(torch.autograd.Function):
@@ -369,6 +386,8 @@ class RPN(nn.Module):
     def forward(self, x, grad_box=None):
         """grad_box: a GradBox in which a later reader of x (the Dev make-up layer) leaves ITS data gradient for x;
         the shared convolution's data-gradient kernel adds it (only when the padding is folded: x itself is read)."""
+        if _act16.is_act16(x):
+            return self._forward16(x)
         c = self.conv_shared
         xp = self.padding(x)
         x = conv_bias_relu(xp, c.weight, c.bias, c.stride, c.padding,
@@ -385,6 +404,25 @@ class RPN(nn.Module):
         probs = self.softmax(logits)
         bbox = both[:, ncls:].permute(0, 2, 3, 1).contiguous().view(x.size(0), -1, 4)
         return [logits, probs, bbox]
+
+    def _forward16(self, x):
+        """A 16-bit channels-last map (MODEL.ACT_SCOPE 'pyramid', inference): the shared convolution reads and writes one,
+        and the two heads are ONE launch over their stacked filters that writes fp32 [N, H, W, 6A] -- the anchors' order, so
+        the outputs are slices of that memory and no permute copy is made.  The filters are stacked per anchor (class a's 2
+        rows, then box a's 4): pixel p, anchor a sits at 6 (p A + a), and [N, H W A, 6] splits into [.., :2] and [.., 2:]."""
+        if self.anchor_stride != 1:
+            raise _lib.FiError("RPN on a 16-bit map: anchor_stride %d is not built (the 3x3 stride-2 convolution has no "
+                               "16-bit kernel); use RPN.ANCHOR_STRIDE = 1 or MODEL.ACT_SCOPE = 'trunk'" % self.anchor_stride)
+        x = _pyr16.conv_bias_act16(x, self.conv_shared, relu=True)
+        A = self.conv_class.weight.shape[0] // 2
+        cin = self.conv_class.weight.shape[1]
+        both = _pyr16.head1x1_16(
+            x, torch.cat((self.conv_class.weight.reshape(A, 2, cin), self.conv_bbox.weight.reshape(A, 4, cin)), 1)
+            .reshape(6 * A, cin, 1, 1),
+            torch.cat((self.conv_class.bias.reshape(A, 2), self.conv_bbox.bias.reshape(A, 4)), 1).reshape(6 * A))
+        rows = both.permute(0, 2, 3, 1).view(x.size(0), -1, 6)       # a view: the memory is [N, H, W, 6A]
+        logits = rows[:, :, :2]
+        return [logits, self.softmax(logits), rows[:, :, 2:]]
 
     @staticmethod
     def dense_at_rows(dense_maps, image, anchor, valid, per_loc):
