@@ -15,6 +15,8 @@ LIB_PATH = os.path.join(_HERE, "libfi_hip.so")
 SOURCES = ["fi_core.hip", "crop_and_resize.hip", "roi_pool.hip", "nms.hip", "sinkhorn.hip",
            "class_mean.hip", "conv_igemm.hip", "conv1x1_ring.hip", "conv3x3_wino.hip", "conv_bf16.hip", "conv_f16.hip", "sgd.hip", "glue.hip", "proposal.hip", "targets.hip", "losses.hip", "dev_stage.hip", "meta_stats.hip"]
 HEADERS = ["fi_common.h", os.path.join("..", "..", "include", "fi_capi.h")]
+# device code that crop_and_resize.hip (libfi_hip.so) and crop_roi16.hip (libfi_roi16.so) share
+CROP_DEV_HEADERS = ["crop_dev.h"]
 # device code that sinkhorn.hip (libfi_hip.so) and sinkhorn_bp.hip (libfi_ot.so) share
 SINKHORN_HEADERS = ["sinkhorn_dev.h"]
 # the evaluation path (inference post-processing, include/fi_eval.h): its own library, linked against libfi_hip.so
@@ -49,6 +51,10 @@ ACT16_HEADERS = ACT16_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_act
 PYR16_LIB_PATH = os.path.join(_HERE, "libfi_pyr16.so")
 PYR16_SOURCES = ["conv_pyr16.hip", "conv_pyr16_f16.hip"]
 PYR16_HEADERS = ACT16_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_pyr16.h")]
+# RoIAlign that reads 16-bit channels-last pyramid maps (include/fi_roi16.h): a ninth library, built the same way
+ROI16_LIB_PATH = os.path.join(_HERE, "libfi_roi16.so")
+ROI16_SOURCES = ["crop_roi16.hip", "crop_roi16_f16.hip"]
+ROI16_HEADERS = CROP_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_roi16.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
@@ -80,6 +86,8 @@ def _compile(sources, headers, force, verbose):
         deps += [os.path.join(CSRC, h) for h in SINKHORN_HEADERS] if s.endswith("sinkhorn.hip") else []
         deps += [os.path.join(CSRC, "conv_act16.hip")] if s.endswith("conv_act16_f16.hip") else []
         deps += [os.path.join(CSRC, "conv_pyr16.hip")] if s.endswith("conv_pyr16_f16.hip") else []
+        deps += [os.path.join(CSRC, h) for h in CROP_DEV_HEADERS] if s.endswith("crop_and_resize.hip") else []
+        deps += [os.path.join(CSRC, "crop_roi16.hip")] if s.endswith("crop_roi16_f16.hip") else []
         if force or _stale(o, deps):
             cmd = [HIPCC] + FLAGS + ["-c", s, "-o", o]
             if verbose:
@@ -91,7 +99,7 @@ def _compile(sources, headers, force, verbose):
 
 def build_hip(force=False, verbose=False):
     """Builds libfi_hip.so, libfi_eval.so, libfi_cocoeval.so, libfi_cocomask.so, libfi_ot.so, libfi_convt.so,
-    libfi_act16.so and libfi_pyr16.so; returns the path of the first."""
+    libfi_act16.so, libfi_pyr16.so and libfi_roi16.so; returns the path of the first."""
     objs = _compile(SOURCES, HEADERS, force, verbose)
     if force or _stale(LIB_PATH, objs):
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
@@ -104,7 +112,8 @@ def build_hip(force=False, verbose=False):
                                   (OT_LIB_PATH, OT_SOURCES, OT_HEADERS),
                                   (CONVT_LIB_PATH, CONVT_SOURCES, CONVT_HEADERS),
                                   (ACT16_LIB_PATH, ACT16_SOURCES, ACT16_HEADERS),
-                                  (PYR16_LIB_PATH, PYR16_SOURCES, PYR16_HEADERS)):
+                                  (PYR16_LIB_PATH, PYR16_SOURCES, PYR16_HEADERS),
+                                  (ROI16_LIB_PATH, ROI16_SOURCES, ROI16_HEADERS)):
         objs = _compile(sources, HEADERS + headers, force, verbose)
         if force or _stale(lib, objs + [LIB_PATH]):
             cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + [

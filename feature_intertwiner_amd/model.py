@@ -295,7 +295,12 @@ class MaskRCNN(nn.Module):
         prepare_step(self)
         p2, p3, p4, p5, p6, _ = self.fpn(images, mode='inference')
         mrcnn_maps = [p2, p3, p4, p5]
-        if _act16.is_act16(p2):
+        up_maps = None
+        if _act16.is_act16(p2) and _pyr16.act_scope(cfg.MODEL) == 'roi':
+            # MODEL.ACT_SCOPE 'roi': nothing is unpacked.  The make-up layer runs ONCE on the 16-bit maps for both Dev
+            # calls below, RoIAlign reads its 16-bit maps, and only the crops (what the heads read) are fp32 NCHW
+            up_maps = self.dev_roi.make_up_maps(mrcnn_maps) if self.dev_roi.use_dev else None
+        elif _act16.is_act16(p2):
             # MODEL.ACT_SCOPE 'pyramid': the RPN reads the 16-bit maps; the Dev stage, RoIAlign and the heads read fp32 NCHW
             mrcnn_maps = [_act16.unpack(p) for p in mrcnn_maps]
         outs = [self.rpn(p) for p in (p2, p3, p4, p5, p6)]
@@ -303,7 +308,7 @@ class MaskRCNN(nn.Module):
         extra = self.external_proposals() if self.external_proposals is not None else None
         proposals, _ = proposal_layer([rpn_probs, rpn_bbox], cfg.RPN.POST_NMS_ROIS_INFERENCE,
                                       cfg.RPN.NMS_THRESHOLD, self.priors, cfg, extra)
-        pooled_cls, _, feat_out = self.dev_roi(mrcnn_maps, proposals)
+        pooled_cls, _, feat_out = self.dev_roi(mrcnn_maps, proposals, up_maps=up_maps)
         small_output_all, small_gt_all = feat_out if feat_out else (None, None)
         _, mrcnn_class, mrcnn_bbox = self.classifier(pooled_cls, small_output_all, small_gt_all)
         meta = torch.as_tensor(image_metas, device=images.device, dtype=torch.float32)
@@ -311,7 +316,7 @@ class MaskRCNN(nn.Module):
         detections = detection_layer(proposals, mrcnn_class, mrcnn_bbox, windows, cfg)
         h, w = float(cfg.DATA.IMAGE_SHAPE[0]), float(cfg.DATA.IMAGE_SHAPE[1])
         scale = const_tensor([h, w, h, w], images.device)
-        _, pooled_mask, _ = self.dev_roi(mrcnn_maps, detections[:, :, :4] / scale)
+        _, pooled_mask, _ = self.dev_roi(mrcnn_maps, detections[:, :, :4] / scale, up_maps=up_maps)
         mrcnn_mask = self.mask(pooled_mask)
         mrcnn_mask = mrcnn_mask.view(bs, -1, mrcnn_mask.size(1), mrcnn_mask.size(2), mrcnn_mask.size(3))
         return [detections, mrcnn_mask]

@@ -30,7 +30,7 @@ SIGNATURES = {
 }
 _pyr16 = None
 _STATS = {"lateral": 0, "head": 0}
-SCOPES = ("trunk", "pyramid")
+SCOPES = ("trunk", "pyramid", "roi")
 
 
 def load():
@@ -62,15 +62,16 @@ def reset_stats():
 
 
 def act_scope(model_cfg):
-    """MODEL.ACT_SCOPE of a configuration's MODEL node: 'trunk' (absent: the 16-bit tensors end behind C5) or 'pyramid'
-    (they run on through p2..p6 to the RPN's outputs).  'pyramid' needs a 16-bit MODEL.ACT_PRECISION; ValueError
+    """MODEL.ACT_SCOPE of a configuration's MODEL node: 'trunk' (absent: the 16-bit tensors end behind C5), 'pyramid'
+    (they run on through p2..p6 to the RPN's outputs) or 'roi' (everything 'pyramid' does, and the make-up layer and
+    RoIAlign read and write them too: roi16).  'pyramid' and 'roi' need a 16-bit MODEL.ACT_PRECISION; ValueError
     otherwise, and for any other value."""
     scope = getattr(model_cfg, "ACT_SCOPE", "trunk")
     act = getattr(model_cfg, "ACT_PRECISION", "fp32")
     if scope not in SCOPES:
-        raise ValueError("MODEL.ACT_SCOPE is 'trunk' or 'pyramid', got %r (MODEL.ACT_PRECISION = %r)" % (scope, act))
-    if scope == "pyramid" and act not in _conv._LOWP:
-        raise ValueError("MODEL.ACT_SCOPE = 'pyramid' needs MODEL.ACT_PRECISION = 'bf16' or 'fp16', got %r" % (act,))
+        raise ValueError("MODEL.ACT_SCOPE is 'trunk', 'pyramid' or 'roi', got %r (MODEL.ACT_PRECISION = %r)" % (scope, act))
+    if scope != "trunk" and act not in _conv._LOWP:
+        raise ValueError("MODEL.ACT_SCOPE = %r needs MODEL.ACT_PRECISION = 'bf16' or 'fp16', got %r" % (scope, act))
     return scope
 
 

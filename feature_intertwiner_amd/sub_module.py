@@ -19,6 +19,7 @@ from . import _lib
 from . import act16 as _act16
 from . import conv as _conv
 from . import pyr16 as _pyr16
+from . import roi16 as _roi16
 from .conv import (Conv2d, ConvTranspose2x2, ConvTranspose3x3, GradBox, conv1x1_class_rows, conv2d, conv_bias_relu,
                    conv_bn_act, convt_bn_act, linear, maxpool3x3s2, take_rows, upsample2x)
 from .intertwiner import class_mean, roi_level
@@ -240,7 +241,7 @@ class FPN(nn.Module):
             if mode == 'train':
                 raise NotImplementedError("MODEL.ACT_PRECISION = %r: training on 16-bit activation tensors is not built "
                                           "(the 16-bit trunk is forward only: mode='inference')" % (act,))
-        scope = _pyr16.act_scope(self.config.MODEL)     # 'pyramid': p2..p6 stay 16-bit as well (_pyramid16)
+        scope = _pyr16.act_scope(self.config.MODEL)     # 'pyramid' / 'roi': p2..p6 stay 16-bit as well (_pyramid16)
         act = act != "fp32" and mode == 'inference' and x.is_cuda and not torch.is_grad_enabled()
         x = conv_bn_act(x, self.C1[0], self.C1[1], relu=True)       # C1 = conv, bn, relu, pad, maxpool
         x = _pad_maxpool(x, self.C1[3], self.C1[4])
@@ -259,7 +260,7 @@ class FPN(nn.Module):
             c[lvl] = stage(c[lvl - 1])
             if first is not None:
                 first.lateral_box = None           # not picked up (the block took another path): nothing is given
-        if act and scope == "pyramid":
+        if act and scope in ("pyramid", "roi"):
             return self._pyramid16(c) + [ot_loss]
         if act:
             c = {lvl: _act16.unpack(m) for lvl, m in c.items()}
@@ -293,7 +294,7 @@ class FPN(nn.Module):
         return [p2, p3, p4, p5, p6, ot_loss]
 
     def _pyramid16(self, c):
-        """[p2 .. p6] as 16-bit channels-last tensors from the 16-bit c2..c5 (MODEL.ACT_SCOPE 'pyramid', inference): nothing
+        """[p2 .. p6] as 16-bit channels-last tensors from the 16-bit c2..c5 (MODEL.ACT_SCOPE 'pyramid' / 'roi', inference): nothing
         is unpacked, each top-down step is ONE launch that reads the coarser level at half resolution (no upsampled map),
         the smoothing convolutions carry their folded padding, and p6 is the stride-2 subsample of p5."""
         p5 = _pyr16.conv_bias_act16(c[5], self.P5_conv1)
@@ -501,6 +502,8 @@ class Dev(nn.Module):
         self.structure = config.DEV.STRUCTURE
         self.roi_type = config.ROIS.METHOD
         self.roi_spatial_scale = [1. / 4, 1. / 8, 1. / 16, 1. / 32]
+        if _pyr16.act_scope(config.MODEL) == 'roi':
+            self._require_roi16()
         if self.use_dev:
             self.feat_pool_size = config.DEV.FEAT_BRANCH_POOL_SIZE
             assert self.feat_pool_size % 2 == 0, 'pool size of feature branch has to be even'
@@ -547,6 +550,10 @@ class Dev(nn.Module):
         return roi_lvl > level if level < 5 else torch.zeros_like(roi_lvl, dtype=torch.bool)
 
     def _crop(self, maps, boxes, box_ind, level, size, grad_group=None):
+        if _act16.is_act16(maps[0]):
+            # MODEL.ACT_SCOPE 'roi' (inference): RoIAlign reads the 16-bit channels-last maps; the crops are fp32 NCHW
+            self._require_roi16()
+            return _roi16.pyramid_crop16(maps, boxes, box_ind, level, size, size)
         if self.roi_type == 'roi_align':
             return pyramid_crop_and_resize(maps, boxes, box_ind, level, size, size, grad_group=grad_group)
         # roi_pool: per level (the RoIPool kernel takes pixel boxes and a per-level scale)
@@ -557,6 +564,16 @@ class Dev(nn.Module):
             if sel.numel():
                 out[sel] = RoIPoolFunction(size, size, self.roi_spatial_scale[i])(maps[i], pix[sel])
         return out
+
+    def _require_roi16(self):
+        """What 16-bit maps (MODEL.ACT_SCOPE = 'roi') cannot run is an error, not another path."""
+        cfg = self.config
+        if self.roi_type != 'roi_align':
+            raise NotImplementedError("MODEL.ACT_SCOPE = 'roi' needs ROIS.METHOD = 'roi_align' (got %r): RoIPool has no "
+                                      "kernel on 16-bit channels-last maps" % (self.roi_type,))
+        if self.use_dev and cfg.DEV.UPSAMPLE_FAC != 1.:
+            raise NotImplementedError("MODEL.ACT_SCOPE = 'roi' needs DEV.UPSAMPLE_FAC = 1 (got %r): the transposed make-up "
+                                      "layer has no 16-bit kernel" % (cfg.DEV.UPSAMPLE_FAC,))
 
     def _make_roi_pool_box_input(self, boxes, box_ind):
         b = boxes * float(self.image_shape[0])      # square images only (SURVEY Q5)
@@ -569,6 +586,12 @@ class Dev(nn.Module):
         gradient for the map -- plus what the big-box crop of forward() left in take_from -- goes to give_to's taker
         (the RPN's shared convolution) instead of to autograd: one kernel writes the map's whole gradient."""
         cfg = self.config
+        if _act16.is_act16(x[0]):
+            # MODEL.ACT_SCOPE 'roi' (inference): one launch per level on the trunk's 3x3 kernel, 16-bit channels-last in and
+            # out (a training-mode BatchNorm raises in conv_bn_act16)
+            self._require_roi16()
+            seqs = [self.upsample[i if cfg.DEV.MULTI_UPSAMPLER else 0] for i in range(len(x))]
+            return [_act16.conv_bn_act16(m, seq[0], seq[1], relu=True) for m, seq in zip(x, seqs)]
 
         def make_up(i, m):
             seq = self.upsample[i if cfg.DEV.MULTI_UPSAMPLER else 0]
