@@ -210,7 +210,7 @@ def planned_kernel(query, *args):
 FWD_FORMS = ("GENERIC", "PATCH", "PATCH_FLAT13", "PATCH_FLAT14", "WINO14", "WINO", "REG1X1", "RING")
 WGRAD_FORMS = ("VEC", "VEC_TWO_TAP", "SCALAR_TAP_MAJOR", "SCALAR_ROW_MAJOR")
 WINDOWS = ("1x1", "3x3", "7x7", "other")
-LAUNCH_FLAGS = {"tap_major": 1, "channels_last": 2, "vec_out": 4, "swizzled": 8, "row_uniform": 16}
+LAUNCH_FLAGS = {"tap_major": 1, "channels_last": 2, "vec_out": 4, "swizzled": 8, "row_uniform": 16, "winograd": 32}
 
 
 def planned_launches(query, *args):

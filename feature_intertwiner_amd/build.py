@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libfi_hip.so")
 SOURCES = ["fi_core.hip", "crop_and_resize.hip", "roi_pool.hip", "nms.hip", "sinkhorn.hip",
-           "class_mean.hip", "conv_igemm.hip", "conv1x1_ring.hip", "conv3x3_wino.hip", "conv_bf16.hip", "conv_f16.hip", "sgd.hip", "glue.hip", "proposal.hip", "targets.hip", "losses.hip", "dev_stage.hip", "meta_stats.hip"]
+           "class_mean.hip", "conv_igemm.hip", "conv1x1_ring.hip", "conv3x3_wino.hip", "conv3x3_wino_wgrad.hip", "conv_bf16.hip", "conv_f16.hip", "sgd.hip", "glue.hip", "proposal.hip", "targets.hip", "losses.hip", "dev_stage.hip", "meta_stats.hip"]
 HEADERS = ["fi_common.h", os.path.join("..", "..", "include", "fi_capi.h")]
 # device code that crop_and_resize.hip (libfi_hip.so) and crop_roi16.hip (libfi_roi16.so) share
 CROP_DEV_HEADERS = ["crop_dev.h"]

@@ -1857,21 +1857,8 @@ int make_geom(ConvGeom &g, int N, int Cin, int H, int W, int Cout, int R, int S,
     FI_REQUIRE((long)N * Cin * H * W < 2147483647L * 2 && (long)Cout * K < 2147483647L, "tensor too large");
     g.K = (int)K;
     g.P = (int)P;
-    auto magic = [](unsigned d, unsigned &mul, unsigned &sft) {
-        if (d <= 1) {
-            mul = 0;
-            sft = 0;
-            return;
-        }
-        unsigned L = 0;
-        while ((1ull << L) < d) ++L;                   // ceil(log2 d)
-        const unsigned total = 31 + L;                 // 2^total / d < 2^32
-        const unsigned long long num = 1ull << total;
-        mul = (unsigned)((num + d - 1) / d);
-        sft = total - 32;                              // L >= 1 for d >= 2
-    };
-    magic((unsigned)(g.OH * g.OW), g.mul_ohw, g.sft_ohw);
-    magic((unsigned)g.OW, g.mul_ow, g.sft_ow);
+    fi::magic_div((unsigned)(g.OH * g.OW), g.mul_ohw, g.sft_ohw);
+    fi::magic_div((unsigned)g.OW, g.mul_ow, g.sft_ow);
     return FI_OK;
 }
 
@@ -1966,6 +1953,11 @@ void launch_wgrad_bm(const FiConvLaunch &l, ConvGeom g, const float *x, const fl
 void launch_wgrad(const FiConvLaunch &l, const ConvGeom &g, const float *x, const float *dy, float *dw, float *dbias,
                   hipStream_t st, const WgradBatch *batch = nullptr)
 {
+    if (l.flags & FI_LAUNCH_WINOGRAD) {          // conv3x3_wino_wgrad.hip (never a batch: plan_wgrad)
+        const fi::WinoWgradArgs a = {x, dy, dw, dbias, g.N, g.Cin, g.H, g.W, g.Cout, l.pixels_per_split / 4, l.splits};
+        fi::launch_conv3x3_wino_wgrad(a, st);
+        return;
+    }
     (l.tile_rows == 64 ? launch_wgrad_bm<64> : launch_wgrad_bm<128>)(l, g, x, dy, dw, dbias, st, batch);
 }
 
@@ -2182,6 +2174,31 @@ void plan_wgrad(FiConvLaunch &l, const ConvGeom &g, int form, int nb, bool batch
     l.grid_x = fi::ceil_div(K, BN);
     l.grid_y = fi::ceil_div(Cout, bm);
     l.grid_z = l.splits;
+    // Winograd F(2x2,3x3) form of the slot (conv3x3_wino_wgrad.hip: 16 MFMAs per 2 x 2 tile where the direct form needs 36):
+    // a single FI_WGRAD_VEC problem -- same-size stride 1, tap-major, Cin % 128 == 0, operands aligned -- on a 3x3 / pad 1
+    // window and a map with even H and W, from 256 input channels (every narrower layer keeps the direct kernel), Cout in
+    // whole blocks of the kernel.  A batch stays on the direct kernel's one launch.  FI_NO_WINOGRAD and
+    // FI_NO_WINOGRAD_WGRAD (both read per call) keep the direct form.  The launch keeps the slot's counter (kernel_id);
+    // tile_rows, the grid, splits and pixels_per_split say what the Winograd kernel does: 64 x 64 blocks, and as many
+    // splits of whole stages of tiles as fill fi::WINO_WG_SLOTS workgroups (one round of the CUs), none under
+    // fi::WINO_WG_MIN_TILES tiles.
+    if (form == FI_WGRAD_VEC && !gemm && !batched && nb == 1 && g.R == 3 && g.S == 3 && g.ph == 1 && g.pw == 1 &&
+        g.H % 2 == 0 && g.W % 2 == 0 && g.Cin >= 256 && Cout % fi::WINO_WG_BLOCK == 0 && !getenv("FI_NO_WINOGRAD") &&
+        !getenv("FI_NO_WINOGRAD_WGRAD")) {
+        const int ntiles = g.N * (g.H / 2) * (g.W / 2);
+        const int blocks = (g.Cin / fi::WINO_WG_BLOCK) * (Cout / fi::WINO_WG_BLOCK);
+        const int max_sp = fi::ceil_div(ntiles, fi::WINO_WG_MIN_TILES);
+        const int want_sp = fi::WINO_WG_SLOTS / blocks;
+        const int sp = want_sp < 1 ? 1 : (want_sp > max_sp ? max_sp : want_sp);
+        const int tps = fi::ceil_div(fi::ceil_div(ntiles, sp), fi::WINO_WG_STAGE) * fi::WINO_WG_STAGE;
+        l.flags = (l.flags & ~FI_LAUNCH_ROW_UNIFORM) | FI_LAUNCH_WINOGRAD | FI_LAUNCH_SWIZZLED;
+        l.tile_rows = fi::WINO_WG_BLOCK;
+        l.pixels_per_split = 4 * tps;
+        l.splits = fi::ceil_div(ntiles, tps);
+        l.grid_x = g.Cin / fi::WINO_WG_BLOCK;
+        l.grid_y = Cout / fi::WINO_WG_BLOCK;
+        l.grid_z = l.splits;
+    }
 }
 
 // -------------------------------------------------------------------------------------

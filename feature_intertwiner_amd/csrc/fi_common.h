@@ -43,6 +43,37 @@ struct WinoArgs {
 };
 void launch_conv3x3_wino_flat(const WinoArgs &a, hipStream_t st);
 
+// conv3x3_wino_wgrad.hip (launched by launch_wgrad when plan_wgrad sets FI_LAUNCH_WINOGRAD): the weight gradient of the same
+// layers over the same 2 x 2 tiles; x / dy NCHW and 16-byte aligned, dW tap-major, the pixel splits add with atomics
+constexpr int WINO_WG_BLOCK = 64;    // a workgroup's Cout and Cin block (Cin and Cout are multiples of it: plan_wgrad)
+constexpr int WINO_WG_STAGE = 4;     // 2 x 2 tiles per LDS stage; a pixel split is a whole number of stages
+constexpr int WINO_WG_SLOTS = 256;   // workgroups blocks x splits may reach: one per CU (82 KB of LDS, 512 registers per lane)
+constexpr int WINO_WG_MIN_TILES = 32;     // fewest tiles of a split (8 stages) unless it is the only one
+struct WinoWgradArgs {
+    const float *x, *dy;
+    float *dw, *dbias;               // dbias may be null
+    int N, Cin, H, W, Cout;
+    int tiles_per_split, splits;     // the plan's cut of the N * H/2 * W/2 tiles
+};
+void launch_conv3x3_wino_wgrad(const WinoWgradArgs &a, hipStream_t st);
+
+// n / d == umulhi(n, mul) >> sft for 0 <= n < 2^31 (mul = ceil(2^(32+sft) / d), 32 + sft = 31 + ceil(log2 d)); mul == 0
+// encodes d == 1
+inline void magic_div(unsigned d, unsigned &mul, unsigned &sft)
+{
+    if (d <= 1) {
+        mul = 0;
+        sft = 0;
+        return;
+    }
+    unsigned L = 0;
+    while ((1ull << L) < d) ++L;                   // ceil(log2 d)
+    const unsigned total = 31 + L;                 // 2^total / d < 2^32
+    const unsigned long long num = 1ull << total;
+    mul = (unsigned)((num + d - 1) / d);
+    sft = total - 32;                              // L >= 1 for d >= 2
+}
+
 #define FI_HIP_CHECK(expr)                                                         \
     do {                                                                           \
         hipError_t _e = (expr);                                                    \

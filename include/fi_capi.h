@@ -516,6 +516,12 @@ int fi_gemm_nt_plan(const float *a, const float *b, const float *scale, const fl
  *   SWIZZLED     FI_WGRAD_VEC with at least 32768 pixels (unless FI_NO_WG_SWZ is set) or with a batch: a 1-D grid of
  *                grid_x * grid_y * grid_z * per_launch workgroups rounded up to a multiple of 8; grid_x/y/z stay the logical
  *                grid (column tiles, Cout tiles, pixel splits)
+ *   WINOGRAD     one FI_WGRAD_VEC problem (never a batch) on a 3x3 / pad 1 window and a map with even H and W, Cin >= 256,
+ *                Cout % 64 == 0: conv3x3_wino_wgrad_kernel in the slot (kernel_id) of the direct kernel.  tile_rows 64;
+ *                grid_x / grid_y the 64-channel blocks of Cin / Cout; the splits are whole stages of 4 tiles of 2 x 2
+ *                pixels (pixels_per_split = 4 x the tiles of a split), as many as fill 256 workgroups, none under 32
+ *                tiles (WINO_WG_SLOTS / WINO_WG_MIN_TILES in csrc/fi_common.h); always SWIZZLED, never ROW_UNIFORM.  FI_NO_WINOGRAD or FI_NO_WINOGRAD_WGRAD in the environment,
+ *                read per call, keep the direct kernel
  *   tile_rows, splits, pixels_per_split   see fi_conv2d_weight_grad_split_plan; per_launch see fi_conv2d_weight_grad_plan */
 enum {
     FI_FWD_GENERIC = 0,
@@ -539,7 +545,8 @@ enum {
     FI_LAUNCH_CHANNELS_LAST = 2,     /* forward: y is [N][OH][OW][Cout] */
     FI_LAUNCH_VEC_OUT = 4,
     FI_LAUNCH_SWIZZLED = 8,
-    FI_LAUNCH_ROW_UNIFORM = 16
+    FI_LAUNCH_ROW_UNIFORM = 16,
+    FI_LAUNCH_WINOGRAD = 32          /* weight gradient: FI_WGRAD_VEC in its Winograd F(2x2,3x3) form */
 };
 typedef struct {
     int32_t form;                    /* FI_FWD_* / FI_WGRAD_* */
