@@ -15,7 +15,8 @@ LIB_PATH = os.path.join(_HERE, "libfi_hip.so")
 SOURCES = ["fi_core.hip", "crop_and_resize.hip", "roi_pool.hip", "nms.hip", "sinkhorn.hip",
            "class_mean.hip", "conv_igemm.hip", "conv1x1_ring.hip", "conv3x3_wino.hip", "conv3x3_wino_wgrad.hip", "conv_bf16.hip", "conv_f16.hip", "sgd.hip", "glue.hip", "proposal.hip", "targets.hip", "losses.hip", "dev_stage.hip", "meta_stats.hip"]
 HEADERS = ["fi_common.h", os.path.join("..", "..", "include", "fi_capi.h")]
-# device code that crop_and_resize.hip (libfi_hip.so) and crop_roi16.hip (libfi_roi16.so) share
+# device code that crop_and_resize.hip (libfi_hip.so), crop_roi16.hip (libfi_roi16.so) and head16_crop.hip
+# (libfi_head16.so) share
 CROP_DEV_HEADERS = ["crop_dev.h"]
 # device code that sinkhorn.hip (libfi_hip.so) and sinkhorn_bp.hip (libfi_ot.so) share
 SINKHORN_HEADERS = ["sinkhorn_dev.h"]
@@ -43,7 +44,8 @@ CONVT_HEADERS = [os.path.join("..", "..", "include", "fi_convt.h")]
 # library, built the same way
 ACT16_LIB_PATH = os.path.join(_HERE, "libfi_act16.so")
 ACT16_SOURCES = ["conv_act16.hip", "conv_act16_f16.hip"]
-# device code that conv_act16.hip (libfi_act16.so) and conv_pyr16.hip (libfi_pyr16.so) share
+# device code that conv_act16.hip (libfi_act16.so), conv_pyr16.hip (libfi_pyr16.so) and head16_out.hip (libfi_head16.so)
+# share
 ACT16_DEV_HEADERS = ["conv_act16_dev.h"]
 ACT16_HEADERS = ACT16_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_act16.h")]
 # the pyramid's lateral step and the RPN's stacked heads on 16-bit channels-last tensors (include/fi_pyr16.h): an eighth
@@ -55,6 +57,11 @@ PYR16_HEADERS = ACT16_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_pyr
 ROI16_LIB_PATH = os.path.join(_HERE, "libfi_roi16.so")
 ROI16_SOURCES = ["crop_roi16.hip", "crop_roi16_f16.hip"]
 ROI16_HEADERS = CROP_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_roi16.h")]
+# the box and mask heads on 16-bit channels-last crops -- RoIAlign that writes them, the fp32 output layer behind them
+# (include/fi_head16.h): a tenth library, built the same way
+HEAD16_LIB_PATH = os.path.join(_HERE, "libfi_head16.so")
+HEAD16_SOURCES = ["head16_crop.hip", "head16_crop_f16.hip", "head16_out.hip", "head16_out_f16.hip"]
+HEAD16_HEADERS = CROP_DEV_HEADERS + ACT16_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_head16.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
@@ -88,6 +95,8 @@ def _compile(sources, headers, force, verbose):
         deps += [os.path.join(CSRC, "conv_pyr16.hip")] if s.endswith("conv_pyr16_f16.hip") else []
         deps += [os.path.join(CSRC, h) for h in CROP_DEV_HEADERS] if s.endswith("crop_and_resize.hip") else []
         deps += [os.path.join(CSRC, "crop_roi16.hip")] if s.endswith("crop_roi16_f16.hip") else []
+        deps += [os.path.join(CSRC, "head16_crop.hip")] if s.endswith("head16_crop_f16.hip") else []
+        deps += [os.path.join(CSRC, "head16_out.hip")] if s.endswith("head16_out_f16.hip") else []
         if force or _stale(o, deps):
             cmd = [HIPCC] + FLAGS + ["-c", s, "-o", o]
             if verbose:
@@ -99,7 +108,7 @@ def _compile(sources, headers, force, verbose):
 
 def build_hip(force=False, verbose=False):
     """Builds libfi_hip.so, libfi_eval.so, libfi_cocoeval.so, libfi_cocomask.so, libfi_ot.so, libfi_convt.so,
-    libfi_act16.so, libfi_pyr16.so and libfi_roi16.so; returns the path of the first."""
+    libfi_act16.so, libfi_pyr16.so, libfi_roi16.so and libfi_head16.so; returns the path of the first."""
     objs = _compile(SOURCES, HEADERS, force, verbose)
     if force or _stale(LIB_PATH, objs):
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
@@ -113,7 +122,8 @@ def build_hip(force=False, verbose=False):
                                   (CONVT_LIB_PATH, CONVT_SOURCES, CONVT_HEADERS),
                                   (ACT16_LIB_PATH, ACT16_SOURCES, ACT16_HEADERS),
                                   (PYR16_LIB_PATH, PYR16_SOURCES, PYR16_HEADERS),
-                                  (ROI16_LIB_PATH, ROI16_SOURCES, ROI16_HEADERS)):
+                                  (ROI16_LIB_PATH, ROI16_SOURCES, ROI16_HEADERS),
+                                  (HEAD16_LIB_PATH, HEAD16_SOURCES, HEAD16_HEADERS)):
         objs = _compile(sources, HEADERS + headers, force, verbose)
         if force or _stale(lib, objs + [LIB_PATH]):
             cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + [

@@ -296,9 +296,12 @@ class MaskRCNN(nn.Module):
         p2, p3, p4, p5, p6, _ = self.fpn(images, mode='inference')
         mrcnn_maps = [p2, p3, p4, p5]
         up_maps = None
-        if _act16.is_act16(p2) and _pyr16.act_scope(cfg.MODEL) == 'roi':
+        scope = _pyr16.act_scope(cfg.MODEL)
+        detect = _act16.is_act16(p2) and scope == 'detect'
+        if _act16.is_act16(p2) and scope in ('roi', 'detect'):
             # MODEL.ACT_SCOPE 'roi': nothing is unpacked.  The make-up layer runs ONCE on the 16-bit maps for both Dev
-            # calls below, RoIAlign reads its 16-bit maps, and only the crops (what the heads read) are fp32 NCHW
+            # calls below, RoIAlign reads its 16-bit maps, and only the crops (what the heads read) are fp32 NCHW.
+            # 'detect': the crops are 16-bit channels-last too and the heads read them as such (head16)
             up_maps = self.dev_roi.make_up_maps(mrcnn_maps) if self.dev_roi.use_dev else None
         elif _act16.is_act16(p2):
             # MODEL.ACT_SCOPE 'pyramid': the RPN reads the 16-bit maps; the Dev stage, RoIAlign and the heads read fp32 NCHW
@@ -308,15 +311,25 @@ class MaskRCNN(nn.Module):
         extra = self.external_proposals() if self.external_proposals is not None else None
         proposals, _ = proposal_layer([rpn_probs, rpn_bbox], cfg.RPN.POST_NMS_ROIS_INFERENCE,
                                       cfg.RPN.NMS_THRESHOLD, self.priors, cfg, extra)
-        pooled_cls, _, feat_out = self.dev_roi(mrcnn_maps, proposals, up_maps=up_maps)
-        small_output_all, small_gt_all = feat_out if feat_out else (None, None)
+        if detect:
+            # MODEL.ACT_SCOPE 'detect': ONE 16-bit channels-last 7 x 7 crop of the proposals, and below one 14 x 14 crop of
+            # the detections; the feature extractor (no reader: DEV.CLS_MERGE_FEAT is refused) and its host read do not run
+            pooled_cls = self.dev_roi.crop16(mrcnn_maps, proposals, self.dev_roi.pool_size, up_maps=up_maps)
+            small_output_all = small_gt_all = None
+        else:
+            pooled_cls, _, feat_out = self.dev_roi(mrcnn_maps, proposals, up_maps=up_maps)
+            small_output_all, small_gt_all = feat_out if feat_out else (None, None)
         _, mrcnn_class, mrcnn_bbox = self.classifier(pooled_cls, small_output_all, small_gt_all)
         meta = torch.as_tensor(image_metas, device=images.device, dtype=torch.float32)
         windows = meta if meta.size(1) == 4 else meta[:, 4:8]
         detections = detection_layer(proposals, mrcnn_class, mrcnn_bbox, windows, cfg)
         h, w = float(cfg.DATA.IMAGE_SHAPE[0]), float(cfg.DATA.IMAGE_SHAPE[1])
         scale = const_tensor([h, w, h, w], images.device)
-        _, pooled_mask, _ = self.dev_roi(mrcnn_maps, detections[:, :, :4] / scale, up_maps=up_maps)
+        if detect:
+            pooled_mask = self.dev_roi.crop16(mrcnn_maps, detections[:, :, :4] / scale, self.dev_roi.mask_pool_size,
+                                              up_maps=up_maps)
+        else:
+            _, pooled_mask, _ = self.dev_roi(mrcnn_maps, detections[:, :, :4] / scale, up_maps=up_maps)
         mrcnn_mask = self.mask(pooled_mask)
         mrcnn_mask = mrcnn_mask.view(bs, -1, mrcnn_mask.size(1), mrcnn_mask.size(2), mrcnn_mask.size(3))
         return [detections, mrcnn_mask]

@@ -30,7 +30,7 @@ SIGNATURES = {
 }
 _pyr16 = None
 _STATS = {"lateral": 0, "head": 0}
-SCOPES = ("trunk", "pyramid", "roi")
+SCOPES = ("trunk", "pyramid", "roi", "detect")
 
 
 def load():
@@ -63,13 +63,14 @@ def reset_stats():
 
 def act_scope(model_cfg):
     """MODEL.ACT_SCOPE of a configuration's MODEL node: 'trunk' (absent: the 16-bit tensors end behind C5), 'pyramid'
-    (they run on through p2..p6 to the RPN's outputs) or 'roi' (everything 'pyramid' does, and the make-up layer and
-    RoIAlign read and write them too: roi16).  'pyramid' and 'roi' need a 16-bit MODEL.ACT_PRECISION; ValueError
+    (they run on through p2..p6 to the RPN's outputs), 'roi' (everything 'pyramid' does, and the make-up layer and
+    RoIAlign read and write them too: roi16) or 'detect' (everything 'roi' does, and the crops and both heads stay 16-bit
+    channels-last up to the fp32 outputs: head16).  Every scope but 'trunk' needs a 16-bit MODEL.ACT_PRECISION; ValueError
     otherwise, and for any other value."""
     scope = getattr(model_cfg, "ACT_SCOPE", "trunk")
     act = getattr(model_cfg, "ACT_PRECISION", "fp32")
     if scope not in SCOPES:
-        raise ValueError("MODEL.ACT_SCOPE is 'trunk', 'pyramid' or 'roi', got %r (MODEL.ACT_PRECISION = %r)" % (scope, act))
+        raise ValueError("MODEL.ACT_SCOPE is 'trunk', 'pyramid', 'roi' or 'detect', got %r (MODEL.ACT_PRECISION = %r)" % (scope, act))
     if scope != "trunk" and act not in _conv._LOWP:
         raise ValueError("MODEL.ACT_SCOPE = %r needs MODEL.ACT_PRECISION = 'bf16' or 'fp16', got %r" % (scope, act))
     return scope

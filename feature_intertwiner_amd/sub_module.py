@@ -18,6 +18,7 @@ import torch.nn.functional as F
 from . import _lib
 from . import act16 as _act16
 from . import conv as _conv
+from . import head16 as _head16
 from . import pyr16 as _pyr16
 from . import roi16 as _roi16
 from .conv import (Conv2d, ConvTranspose2x2, ConvTranspose3x3, GradBox, conv1x1_class_rows, conv2d, conv_bias_relu,
@@ -241,7 +242,7 @@ class FPN(nn.Module):
             if mode == 'train':
                 raise NotImplementedError("MODEL.ACT_PRECISION = %r: training on 16-bit activation tensors is not built "
                                           "(the 16-bit trunk is forward only: mode='inference')" % (act,))
-        scope = _pyr16.act_scope(self.config.MODEL)     # 'pyramid' / 'roi': p2..p6 stay 16-bit as well (_pyramid16)
+        scope = _pyr16.act_scope(self.config.MODEL)     # all but 'trunk': p2..p6 stay 16-bit as well (_pyramid16)
         act = act != "fp32" and mode == 'inference' and x.is_cuda and not torch.is_grad_enabled()
         x = conv_bn_act(x, self.C1[0], self.C1[1], relu=True)       # C1 = conv, bn, relu, pad, maxpool
         x = _pad_maxpool(x, self.C1[3], self.C1[4])
@@ -260,7 +261,7 @@ class FPN(nn.Module):
             c[lvl] = stage(c[lvl - 1])
             if first is not None:
                 first.lateral_box = None           # not picked up (the block took another path): nothing is given
-        if act and scope in ("pyramid", "roi"):
+        if act and scope != "trunk":
             return self._pyramid16(c) + [ot_loss]
         if act:
             c = {lvl: _act16.unpack(m) for lvl, m in c.items()}
@@ -502,7 +503,7 @@ class Dev(nn.Module):
         self.structure = config.DEV.STRUCTURE
         self.roi_type = config.ROIS.METHOD
         self.roi_spatial_scale = [1. / 4, 1. / 8, 1. / 16, 1. / 32]
-        if _pyr16.act_scope(config.MODEL) == 'roi':
+        if _pyr16.act_scope(config.MODEL) in ('roi', 'detect'):
             self._require_roi16()
         if self.use_dev:
             self.feat_pool_size = config.DEV.FEAT_BRANCH_POOL_SIZE
@@ -566,14 +567,32 @@ class Dev(nn.Module):
         return out
 
     def _require_roi16(self):
-        """What 16-bit maps (MODEL.ACT_SCOPE = 'roi') cannot run is an error, not another path."""
+        """What 16-bit maps (MODEL.ACT_SCOPE = 'roi' / 'detect') cannot run is an error, not another path."""
         cfg = self.config
+        scope = getattr(cfg.MODEL, "ACT_SCOPE", "roi")
         if self.roi_type != 'roi_align':
-            raise NotImplementedError("MODEL.ACT_SCOPE = 'roi' needs ROIS.METHOD = 'roi_align' (got %r): RoIPool has no "
-                                      "kernel on 16-bit channels-last maps" % (self.roi_type,))
+            raise NotImplementedError("MODEL.ACT_SCOPE = %r needs ROIS.METHOD = 'roi_align' (got %r): RoIPool has no "
+                                      "kernel on 16-bit channels-last maps" % (scope, self.roi_type))
         if self.use_dev and cfg.DEV.UPSAMPLE_FAC != 1.:
-            raise NotImplementedError("MODEL.ACT_SCOPE = 'roi' needs DEV.UPSAMPLE_FAC = 1 (got %r): the transposed make-up "
-                                      "layer has no 16-bit kernel" % (cfg.DEV.UPSAMPLE_FAC,))
+            raise NotImplementedError("MODEL.ACT_SCOPE = %r needs DEV.UPSAMPLE_FAC = 1 (got %r): the transposed make-up "
+                                      "layer has no 16-bit kernel" % (scope, cfg.DEV.UPSAMPLE_FAC))
+
+    def crop16(self, x, rois, size, up_maps=None):
+        """MODEL.ACT_SCOPE 'detect' (inference): ONE size x size RoIAlign of `rois` [bs, R, 4] as a 16-bit channels-last
+        tensor [bs * R, depth, size, size] -- of the make-up maps (`up_maps`, or make_up_maps(x) when the caller has
+        none), or of the raw 16-bit p2..p5 `x` with DEV.SWITCH off.  Nothing else of forward() runs: no second crop, no
+        feature extractor and hence no host read of the level counts."""
+        self._require_roi16()
+        maps = x
+        if self.use_dev:
+            if self.structure != 'beta':
+                raise NotImplementedError("only DEV.STRUCTURE='beta' executes in the reference (SURVEY Q9)")
+            maps = up_maps if up_maps is not None else self.make_up_maps(x)
+        bs, R = rois.size(0), rois.size(1)
+        boxes = rois.reshape(-1, 4)
+        box_ind = torch.arange(bs, device=rois.device, dtype=torch.int32).repeat_interleave(R)
+        level = roi_level(boxes, float(self.image_shape[0] * self.image_shape[1]), self.config.ROIS.ASSIGN_ANCHOR_BASE)
+        return _head16.pyramid_crop16_cl(maps, boxes, box_ind, level, size, size)
 
     def _make_roi_pool_box_input(self, boxes, box_ind):
         b = boxes * float(self.image_shape[0])      # square images only (SURVEY Q5)
@@ -926,6 +945,9 @@ class Classifier(nn.Module):
     def __init__(self, depth, num_classes, pool_size, config):
         super(Classifier, self).__init__()
         self.depth, self.pool_size, self.num_classes, self.config = depth, pool_size, num_classes, config
+        if _pyr16.act_scope(config.MODEL) == 'detect' and config.DEV.CLS_MERGE_FEAT:
+            raise NotImplementedError("MODEL.ACT_SCOPE = 'detect' needs DEV.CLS_MERGE_FEAT = False: the feature extractor "
+                                      "whose output it merges has no 16-bit kernel (its stride-2 3x3 layer) and does not run")
         _conv_bn(self, 1, depth, 1024, pool_size)
         self.conv1.full_window = pool_size > 1
         _conv_bn(self, 2, 1024, 1024, 1)
@@ -935,6 +957,8 @@ class Classifier(nn.Module):
         self.linear_bbox = nn.Linear(1024, num_classes * 4)
 
     def forward(self, x, small_feat_input=None, small_gt_index=None, mode='train'):
+        if _act16.is_act16(x):
+            return self._forward16(x, small_feat_input)
         x = conv_bn_act(x, self.conv1, self.bn1, relu=True)
         cfg = self.config
         if cfg.DEV.SWITCH and cfg.DEV.CLS_MERGE_FEAT and cfg.DEV.STRUCTURE == 'beta' and small_feat_input is not None:
@@ -963,6 +987,21 @@ class Classifier(nn.Module):
         return [logits, probs, bbox]
 
 
+    def _forward16(self, x, small_feat_input=None):
+        """16-bit channels-last crops [n, depth, 7, 7] (MODEL.ACT_SCOPE 'detect', inference): the full-window layer on the
+        crop viewed as one row of 49 * depth values, the 1x1 layer, and ONE fp32 output launch over the stacked class and
+        box filters whose [n, 405] rows the logits and boxes are sliced from.  Three launches; only the outputs are fp32."""
+        if small_feat_input is not None and self.config.DEV.SWITCH and self.config.DEV.CLS_MERGE_FEAT:
+            raise NotImplementedError("DEV.CLS_MERGE_FEAT on 16-bit crops is not built")
+        x = _head16.window_bn_act16(x, self.conv1, self.bn1, relu=True)
+        x = _head16.conv_bn_act16(x, self.conv2, self.bn2, relu=True)
+        w, b = _head16.stacked_linear16((self.linear_class, self.linear_bbox), x.dtype)
+        heads = _head16.out1x1_16(x, w, b, act=_head16.NONE, layout=_head16.ROWS)
+        nc = self.linear_class.weight.shape[0]
+        logits, bbox = heads[:, :nc].contiguous(), heads[:, nc:].contiguous()
+        return [logits, self.softmax(logits), bbox.view(bbox.size(0), -1, 4)]
+
+
 class Mask(nn.Module):
     """Mask head (lib/sub_module.py:750-787): four 3x3 conv+BN+ReLU, 2x2 stride-2 deconv, 1x1 conv to classes."""
 
@@ -987,6 +1026,10 @@ class Mask(nn.Module):
         select_class [N] (training, with shuffled=False and activate=False): return only the logits of class
         select_class[n] for RoI n, [N, 2, 2, 14, 14] -- conv5 still evaluates every class (the reference's schedule), but
         its backward then knows that the gradient has one non-zero channel per RoI (conv.conv1x1_class_rows)."""
+        if _act16.is_act16(x):
+            if not (shuffled and activate) or select_class is not None:
+                raise _lib.FiError("Mask on 16-bit crops is the inference form: shuffled, activated, every class")
+            return self._forward16(x)
         # input_grad_box: x has another reader whose backward runs later and takes the gradient from there (Dev.forward)
         give = input_grad_box if (input_grad_box is not None and input_grad_box.taker and _fused_path(x, self.bn1)) else None
         x = conv_bn_act(x, self.conv1, self.bn1, relu=True, dx_give_to=give)
@@ -1021,3 +1064,14 @@ class Mask(nn.Module):
         if not shuffled:
             return y
         return y.permute(0, 3, 4, 1, 5, 2).reshape(n, y.shape[3], 2 * h, 2 * w)
+
+    def _forward16(self, x):
+        """16-bit channels-last crops [n, depth, 14, 14] (MODEL.ACT_SCOPE 'detect', inference): four 3x3 layers and the
+        transposed convolution as a 1x1 layer to (a, b, c) channels on 16-bit tensors, then ONE launch for conv5, the
+        sigmoid and the pixel shuffle that writes [n, K, 28, 28] fp32: no fp32 u, no permute copy, conv5 not padded."""
+        x = _head16.conv_bn_act16(x, self.conv1, self.bn1, relu=True)
+        x = _head16.conv_bn_act16(x, self.conv2, self.bn2, relu=True)
+        x = _head16.conv_bn_act16(x, self.conv3, self.bn3, relu=True)
+        x = _head16.conv_bn_act16(x, self.conv4, self.bn4, relu=True)
+        u = _head16.deconv2x2_act16(x, self.deconv, relu=True)
+        return _head16.out1x1_16(u, self.conv5.weight, self.conv5.bias, act=_head16.SIGMOID, layout=_head16.SHUFFLE)
