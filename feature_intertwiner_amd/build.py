@@ -62,6 +62,11 @@ ROI16_HEADERS = CROP_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_roi1
 HEAD16_LIB_PATH = os.path.join(_HERE, "libfi_head16.so")
 HEAD16_SOURCES = ["head16_crop.hip", "head16_crop_f16.hip", "head16_out.hip", "head16_out_f16.hip"]
 HEAD16_HEADERS = CROP_DEV_HEADERS + ACT16_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_head16.h")]
+# the backward operators of a convolution on 16-bit channels-last tensors -- ReLU mask + column sums, data gradient,
+# weight gradient (include/fi_grad16.h): an eleventh library, built the same way
+GRAD16_LIB_PATH = os.path.join(_HERE, "libfi_grad16.so")
+GRAD16_SOURCES = ["conv_grad16.hip", "conv_grad16_f16.hip"]
+GRAD16_HEADERS = ACT16_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_grad16.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
@@ -97,6 +102,7 @@ def _compile(sources, headers, force, verbose):
         deps += [os.path.join(CSRC, "crop_roi16.hip")] if s.endswith("crop_roi16_f16.hip") else []
         deps += [os.path.join(CSRC, "head16_crop.hip")] if s.endswith("head16_crop_f16.hip") else []
         deps += [os.path.join(CSRC, "head16_out.hip")] if s.endswith("head16_out_f16.hip") else []
+        deps += [os.path.join(CSRC, "conv_grad16.hip")] if s.endswith("conv_grad16_f16.hip") else []
         if force or _stale(o, deps):
             cmd = [HIPCC] + FLAGS + ["-c", s, "-o", o]
             if verbose:
@@ -108,7 +114,7 @@ def _compile(sources, headers, force, verbose):
 
 def build_hip(force=False, verbose=False):
     """Builds libfi_hip.so, libfi_eval.so, libfi_cocoeval.so, libfi_cocomask.so, libfi_ot.so, libfi_convt.so,
-    libfi_act16.so, libfi_pyr16.so, libfi_roi16.so and libfi_head16.so; returns the path of the first."""
+    libfi_act16.so, libfi_pyr16.so, libfi_roi16.so, libfi_head16.so and libfi_grad16.so; returns the path of the first."""
     objs = _compile(SOURCES, HEADERS, force, verbose)
     if force or _stale(LIB_PATH, objs):
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
@@ -123,7 +129,8 @@ def build_hip(force=False, verbose=False):
                                   (ACT16_LIB_PATH, ACT16_SOURCES, ACT16_HEADERS),
                                   (PYR16_LIB_PATH, PYR16_SOURCES, PYR16_HEADERS),
                                   (ROI16_LIB_PATH, ROI16_SOURCES, ROI16_HEADERS),
-                                  (HEAD16_LIB_PATH, HEAD16_SOURCES, HEAD16_HEADERS)):
+                                  (HEAD16_LIB_PATH, HEAD16_SOURCES, HEAD16_HEADERS),
+                                  (GRAD16_LIB_PATH, GRAD16_SOURCES, GRAD16_HEADERS)):
         objs = _compile(sources, HEADERS + headers, force, verbose)
         if force or _stale(lib, objs + [LIB_PATH]):
             cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + [

@@ -10,7 +10,7 @@ Pure Python on tensor attributes (data_ptr(), _version, shape): no library call,
 import collections
 import weakref
 
-WT, FRAG, LOWP, HEAD = "wt", "frag", "lowp", "head"
+WT, FRAG, LOWP, HEAD, WT16 = "wt", "frag", "lowp", "head", "wt16"
 # kind -> what a lookup must expect of the copy:
 #   WT    W^T [Cin][R][S][Cout] of a weight         (scaled: eval-BatchNorm scale folded in or not, shape of the weight)
 #   FRAG  fragment-major copy of a 1x1 matrix       (rows, cols)
@@ -18,6 +18,8 @@ WT, FRAG, LOWP, HEAD = "wt", "frag", "lowp", "head"
 #   HEAD  re-laid-out 16-bit operand of a head layer on 16-bit crops (head16.py), possibly stacked from several tensors and
 #         with an fp32 bias next to it; the record is the FIRST tensor's   (what, dtype, ((address, version) of each
 #         further tensor))
+#   WT16  16-bit data-gradient operand of a layer on 16-bit activations (grad16.py): W^T [Cin][R][S][Cout] with the taps
+#         flipped and the eval-BatchNorm scale folded in, rounded once   (dtype, the fold's key: conv._fold_key)
 
 WITH_SOURCE = object()      # the version of a record whose source is itself a copy (a W^T tensor): the batched transpose
                             # rewrites it in place without a version bump; its copies are dropped when it is republished
