@@ -2224,7 +2224,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_kernel(const float *__restrict
                                                          float *__restrict__ dz, float *__restrict__ g_out,
                                                          float *__restrict__ dshift,
                                                          float *__restrict__ dgamma, float *__restrict__ dbias,
-                                                         int imgs_per_block)
+                                                         int imgs_per_block, int vec16)
 {
     __shared__ float s_a[4], s_b[4];
     const int c = blockIdx.x;
@@ -2233,7 +2233,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_kernel(const float *__restrict
     const float sc = scale[c];
     const float be = beta ? beta[c] : 0.0f;
     float sum_g = 0.0f, sum_gy = 0.0f;
-    const bool vec = (HW & 3) == 0;
+    const bool vec = vec16 != 0;        // HW % 4 == 0 and 16-byte aligned tensors (the launcher's test)
     const bool norelu = relu == 0;
     auto group = [&](const float4 d, float4 v, const float4 r, size_t at) {
         float4 g;
@@ -2278,8 +2278,9 @@ __global__ __launch_bounds__(256) void bn_act_bwd_kernel(const float *__restrict
         }
     }
     if (!vec) {
-        // planes whose size is not a multiple of 4 (7x7 = 49: RoI heads): the workgroup walks the flattened
-        // (image, element) index of its channel, so all 256 lanes stay busy on planes smaller than 256
+        // planes whose size is not a multiple of 4 (7x7 = 49: RoI heads) or tensors off a 16-byte boundary: the
+        // workgroup walks the flattened (image, element) index of its channel, so all 256 lanes stay busy on planes
+        // smaller than 256
         const int total = (n1 - n0) * HW;
         for (int idx = threadIdx.x; idx < total; idx += 256) {
             const int n = idx / HW;
@@ -2611,11 +2612,14 @@ int fi_bn_act_backward(const float *dy, const float *y, const float *scale, cons
     if (chunks < 1) chunks = 1;
     const int ipb = fi::ceil_div(N, chunks);
     chunks = fi::ceil_div(N, ipb);
+    // 16-byte accesses need whole groups per plane and aligned tensors; otherwise the scalar loop
+    const int vec = ((HW & 3) == 0 && (((uintptr_t)dy | (uintptr_t)y | (uintptr_t)residual | (uintptr_t)dz |
+                                        (uintptr_t)g_out) & 15) == 0) ? 1 : 0;
     fi::ProfScope prof(FI_K_BN_ACT_BWD, st);
     auto k = residual ? (g_out ? bn_act_bwd_kernel<true, true> : bn_act_bwd_kernel<true, false>)
                       : (g_out ? bn_act_bwd_kernel<false, true> : bn_act_bwd_kernel<false, false>);
     hipLaunchKernelGGL(k, dim3(C, chunks), dim3(256), 0, st, dy, y, scale, gamma, beta, residual,
-                       N, C, HW, relu, dz, g_out, dshift, dgamma, dbias, ipb);
+                       N, C, HW, relu, dz, g_out, dshift, dgamma, dbias, ipb, vec);
     FI_HIP_CHECK(hipGetLastError());
     return FI_OK;
 }

@@ -380,6 +380,8 @@ int fi_bn_fold_grad_batch(float *const *dw, const float *const *w, const float *
  * that was folded into the shift.  flags: FI_OUTPUTS_ZEROED = the caller has already zero-filled the
  * accumulated outputs (dshift, dgamma, dbias; dweight, dbias of fi_conv2d_weight_grad), e.g. as slices of
  * one arena cleared once per step, so the per-call fills are skipped.
+ * No alignment is required of dy, y, residual, dz, g_out: layout 0 uses 16-byte accesses when HW % 4 == 0 and all of
+ * them are 16-byte aligned, and element accesses otherwise.
  * dgamma recovers x_hat = (y - residual - beta) / gamma from the forward's rounded output: where gamma[c] == 0, y holds
  * no x_hat and NOTHING is added to dgamma[c] (the true gradient sum g * x_hat is in general not zero), and elsewhere
  * the error of dgamma[c] grows with (|y| + |residual| + |beta[c]|) / |gamma[c]| per term.  The fp32 step's default
@@ -616,7 +618,9 @@ int fi_proposal_candidates_ws(const float *probs, int prob_stride, int prob_offs
                               int pre_nms, const float *bbox_std_host, float window_h, float window_w, float *dets,
                               void *workspace, size_t workspace_bytes, fi_stream_t stream);
 /* proposals[b][j] = dets[b][keep[b][j]][0:4] / (norm_h, norm_w, norm_h, norm_w) for j < num[b], zero rows after
- * (lib/layers.py:131-137 without the host-side truncation to the shortest keep list). */
+ * (lib/layers.py:131-137 without the host-side truncation to the shortest keep list).  Only the first
+ * min(num[b], keep_stride) entries of a keep list are read; an entry outside [0, pre_nms) gives a row of zeros.
+ * det_stride >= 4; proposals 16-byte aligned. */
 int fi_proposal_gather(const float *dets, int pre_nms, int det_stride, const int64_t *keep, int keep_stride,
                        const int32_t *num, int batch, int proposal_count, float norm_h, float norm_w,
                        float *proposals, fi_stream_t stream);

@@ -8,7 +8,9 @@ pattern and the address modulo 16 of every pointer (plus what the handlers' `ext
 arrays, device descriptor tables, aliasing).  Each distinct record is replayed on fresh seeded operands at the same
 misalignment, shaped like the step's (exact zeros in ReLU outputs and gates, all-zero class rows, padding rows, level
 starts and map borders, distinct indices, a gamma == 0 channel and |beta| / |gamma| >> 1).  Write-only outputs are
-pre-filled with NaN; accumulated ones with random finite values and checked by their increment.  The clip + SGD step is
+pre-filled with NaN; accumulated ones with random finite values and checked by their increment.  Every operand built at
+a chosen misalignment sits between two guard zones of sentinel floats, which must be intact after the launch (a store a
+few elements before a buffer or past its tail is an error even where the allocation has room).  The clip + SGD step is
 checked in-step: every parameter, gradient and momentum buffer is snapshotted before optim.clip_and_step.
 
 fi_bn_act_backward and gamma == 0: the kernel recovers xhat as (y - beta) / gamma from the forward's output, which holds
@@ -236,14 +238,43 @@ class _Ctx(object):
         return ga, be
 
 
+GUARD = 64                              # sentinel floats on either side of every _at / _place buffer (256 bytes: the
+SENTINEL = -6.0221e23                   # address modulo 16 is that of `align`)
+_GUARDED = []                           # (base, first element of the view, n) since the last _call
+
+
 def _at(n, align, fill=float("nan")):
-    """n floats starting `align` bytes past a 16-byte boundary (a storage offset into a larger buffer)."""
+    """n floats starting `align` bytes past a 16-byte boundary (a storage offset into a larger buffer), between two
+    guard zones of GUARD sentinel floats that _call checks after the launch."""
     assert align % 4 == 0, align
-    base = torch.empty(n + 4, device=DEV, dtype=torch.float32)
-    t = base[align // 4: align // 4 + n]
+    base = torch.empty(n + 2 * GUARD + 4, device=DEV, dtype=torch.float32)
+    lo = GUARD + align // 4
+    base[:lo] = SENTINEL
+    base[lo + n:] = SENTINEL
+    t = base[lo: lo + n]
+    assert t.data_ptr() % 16 == align % 16, (t.data_ptr(), align)
     if fill is not None:
         t.fill_(fill)
+    _GUARDED.append((base, lo, n))
     return t
+
+
+def _check_guards(what):
+    """Every sentinel around the operands built since the last call is intact (a store before a buffer or past its
+    tail lands in one); forgets the buffers."""
+    zones, _GUARDED[:] = list(_GUARDED), []
+    if not zones:
+        return
+    hit = torch.stack([(base[:lo] != SENTINEL).any() | (base[lo + n:] != SENTINEL).any() for base, lo, n in zones])
+    if bool(hit.any()):
+        msgs = []
+        for k in torch.nonzero(hit).reshape(-1).tolist():
+            base, lo, n = zones[k]
+            before = torch.nonzero(base[:lo] != SENTINEL).reshape(-1) - lo
+            after = torch.nonzero(base[lo + n:] != SENTINEL).reshape(-1)
+            msgs.append("operand %d (%d floats): elements %s before its start, %s past its end overwritten" % (
+                k, n, before.tolist()[:8], after.tolist()[:8]))
+        raise AssertionError("%s wrote outside its operands: %s" % (what, "; ".join(msgs)))
 
 
 def _place(src, align):
@@ -270,11 +301,15 @@ def _call(name, I, P):
             args.append(_lib.ptr(v) if (v is None or torch.is_tensor(v)) else v)
     _lib.check(getattr(_lib.load(), name)(*args), "replay " + name)
     torch.cuda.synchronize()
+    _check_guards("%s %s" % (name, I))
 
 
-def _exact(got, ref, what):
+def _exact(got, ref, what, nan_equal=False):
+    """nan_equal: a NaN where the reference holds a NaN counts as equal (inputs with NaN planted on purpose)."""
     got, ref = got.double(), ref.double()
     bad = ~(got == ref)
+    if nan_equal:
+        bad &= ~(torch.isnan(got) & torch.isnan(ref))
     if bool(bad.any()):
         i = int(torch.nonzero(bad.reshape(-1))[0])
         raise AssertionError("%s: element %d of %d not bit-exact (got %r, ref %r; %d elements differ)" % (
@@ -289,6 +324,8 @@ def _h_bn_act(name, I, nul, al, ex, ctx):
     xh = ctx.randn(N, C, HW)
     if has_gamma:
         ga, be = ctx.gamma_beta(C)
+        if dict(ex).get("live_gamma"):            # C == 1: the only channel would be the gamma == 0 one
+            ga[0] = 0.75
         if nul["beta"]:                           # the kernel then takes beta = 0
             be = torch.zeros_like(be)
         inv = 0.5 + ctx.rand(C)
@@ -310,15 +347,22 @@ def _h_bn_act(name, I, nul, al, ex, ctx):
          "residual": None if res is None else _place(res, al.get("residual", 0)),
          "dz": _at(N * C * HW, al.get("dz", 0)).view(N, C, HW),
          "g_out": None if nul["g_out"] else _at(N * C * HW, al.get("g_out", 0)).view(N, C, HW)}
-    sums = _at(3 * C, al.get("dshift", 0), None)
-    if zeroed:
-        _random_fill(sums, ctx)
+    if dict(ex).get("split_sums"):                # three buffers of their own (the step's are slices of one arena)
+        parts = [_at(C, al.get(k, 0), None) for k in ("dshift", "dgamma", "dbias")]
+        for t in parts:
+            _random_fill(t, ctx) if zeroed else t.fill_(float("nan"))
+        before = torch.cat(parts)
     else:
-        sums.fill_(float("nan"))
-    before = sums.clone()
-    P["dshift"] = sums[:C]
-    P["dgamma"] = None if nul["dgamma"] else sums[C:2 * C]
-    P["dbias"] = None if nul["dbias"] else sums[2 * C:]
+        sums = _at(3 * C, al.get("dshift", 0), None)
+        if zeroed:
+            _random_fill(sums, ctx)
+        else:
+            sums.fill_(float("nan"))
+        before = sums.clone()
+        parts = [sums[:C], sums[C:2 * C], sums[2 * C:]]
+    P["dshift"] = parts[0]
+    P["dgamma"] = None if nul["dgamma"] else parts[1]
+    P["dbias"] = None if nul["dbias"] else parts[2]
     _call(name, I, P)
     what = "%s %s" % (name, I)
     g32 = torch.where(y > 0, dy, torch.zeros_like(dy)) if relu else dy
@@ -455,15 +499,20 @@ def _class_rows(N, K, ctx):
 def _h_class_row(name, I, nul, al, ex, ctx):
     from feature_intertwiner_amd import _lib
     N, C, HW, K, gated = I["N"], I["C"], I["HW"], I["num_classes"], I["gated"]
+    opt = dict(ex)        # dead: fraction of all-zero rows; dead_rows: leading rows forced dead; unused_class: no row has it
+    frac, lead, unused = opt.get("dead", 0.75), opt.get("dead_rows", 0), opt.get("unused_class")
     d = ctx.randn(N, HW)
-    dead = ctx.rand(N) < 0.75
+    dead = ctx.rand(N) < frac
     d[dead] = 0.0
-    if N > 2:
+    if N > 2 and frac < 1.0 and lead <= 2:
         d[2] = 0.0
         d[2, HW // 2] = 1.5                                  # one row with a single non-zero
+    d[:lead] = 0.0
     x = ctx.relu_out(N, C, HW)
     w = ctx.randn(K, C)
     cls = _class_rows(N, K, ctx)
+    if unused is not None:
+        cls[cls == unused] = (unused + 1) % K
     dx = None if nul["dx"] else _at(N * C * HW, al.get("dx", 0)).view(N, C, HW)
     dwt = None if nul["dweight"] else _random_fill(torch.empty(K, C, device=DEV), ctx)
     dbt = None if nul["dbias"] else _random_fill(torch.empty(K, device=DEV), ctx)
@@ -483,12 +532,20 @@ def _h_class_row(name, I, nul, al, ex, ctx):
         worst = R.check_increment(dwt, w0, rdw, mw, nk[:, None].expand_as(rdw), what + " dweight")
     if dbt is not None:
         worst = max(worst, R.check_increment(dbt, b0, rdb, mb, nk, what + " dbias"))
+    if unused is not None:                                   # nothing is added to the rows of a class without rows
+        if dwt is not None:
+            _exact(dwt[unused], w0[unused], what + " dweight of the unused class")
+        if dbt is not None:
+            _exact(dbt[unused], b0[unused], what + " dbias of the unused class")
     return worst
 
 
-def _patch_operands(I, ex, ctx, B=2):
+def _patch_operands(I, ex, ctx):
+    """ex beyond the level sizes: B (images, 2), pad (fraction of padding rows, 0.1), dup (the last `dup` rows repeat row
+    0's image and anchor, 0)."""
     ex = dict(ex)
     hs, ws = ex["heights"], ex["widths"]
+    B, pad, dup = ex.get("B", 2), ex.get("pad", 0.1), ex.get("dup", 0)
     per, rows, C = I["per_loc"], I["rows"], I["channels"]
     counts = [h * w * per for h, w in zip(hs, ws)]
     total = sum(counts)
@@ -500,7 +557,11 @@ def _patch_operands(I, ex, ctx, B=2):
     k = min(len(special), rows)
     anchor[:k] = torch.tensor(special[:k], device=DEV)
     image = torch.randint(0, B, (rows,), generator=ctx.g, device=DEV)
-    image[ctx.rand(rows) < 0.1] = -1                         # padding rows
+    image[ctx.rand(rows) < pad] = -1                         # padding rows
+    if dup:
+        image[0] = B - 1
+        image[rows - dup:] = image[0]
+        anchor[rows - dup:] = anchor[0]
     shapes = [(B, C, h, w) for h, w in zip(hs, ws)]
     return shapes, image.to(torch.int64), anchor.to(torch.int64)
 
@@ -556,7 +617,7 @@ def _h_rows_combine(name, I, nul, al, ex, ctx):
     S = rows + 3
     src = ctx.randn(S, L)
     src_row = ctx.perm(S)[:rows].clone()
-    src_row[ctx.rand(rows) < 0.3] = -1
+    src_row[ctx.rand(rows) < dict(ex).get("neg", 0.3)] = -1      # neg: the fraction of rows nothing is gathered into
     dst = _at(rows * L, al.get("dst", 0)).view(rows, L)
     _call(name, I, {"front": front, "src": _place(src, al.get("src", 0)), "src_row": src_row, "dst": dst})
     ref = torch.where((src_row >= 0)[:, None], src[src_row.clamp_min(0)], torch.zeros(rows, L, device=DEV))
@@ -565,24 +626,34 @@ def _h_rows_combine(name, I, nul, al, ex, ctx):
     return _exact(dst, ref, "%s %s" % (name, I))
 
 
-def _pool_input(P, H, W, ctx):
-    x = ctx.relu_out(P, H, W)
-    x[:, ::3] = torch.relu(torch.round(x[:, ::3] * 2) * 0.5)        # ties
+def _pool_input(P, H, W, ctx, ex=()):
+    """A ReLU output with ties, as the stem's; ex `signed`: values of both signs with ties and plane 0 all negative (no
+    window of it holds a zero or a positive); ex `nan`: that many NaN at random places."""
+    opt = dict(ex)
+    if opt.get("signed"):
+        x = ctx.randn(P, H, W)
+        x[:, ::3] = torch.round(x[:, ::3] * 2) * 0.5
+        x[0] = -x[0].abs() - 0.5
+    else:
+        x = ctx.relu_out(P, H, W)
+        x[:, ::3] = torch.relu(torch.round(x[:, ::3] * 2) * 0.5)        # ties
+    if opt.get("nan"):
+        x.view(-1)[ctx.perm(x.numel())[:opt["nan"]]] = float("nan")
     return x
 
 
 def _h_pool_fwd(name, I, nul, al, ex, ctx):
     P, H, W = I["planes"], I["height"], I["width"]
-    x = _place(_pool_input(P, H, W, ctx), al.get("x", 0))
+    x = _place(_pool_input(P, H, W, ctx, ex), al.get("x", 0))
     ref = torch.nn.functional.max_pool2d(x.view(1, P, H, W), 3, 2, 0, ceil_mode=True)[0]
     y = _at(ref.numel(), al.get("y", 0)).view(ref.shape)
     _call(name, I, {"x": x, "y": y})
-    return _exact(y, ref, "%s %s" % (name, I))
+    return _exact(y, ref, "%s %s" % (name, I), nan_equal=bool(dict(ex).get("nan")))
 
 
 def _h_pool_bwd(name, I, nul, al, ex, ctx):
     P, H, W = I["planes"], I["height"], I["width"]
-    x = _place(_pool_input(P, H, W, ctx), al.get("x", 0))
+    x = _place(_pool_input(P, H, W, ctx, ex), al.get("x", 0))
     xr = x.detach().clone().view(1, P, H, W).requires_grad_(True)
     yr = torch.nn.functional.max_pool2d(xr, 3, 2, 0, ceil_mode=True)
     dy = ctx.randn(*yr.shape)
@@ -709,13 +780,20 @@ def _h_gather_props(name, I, nul, al, ex, ctx):
         torch.randint(0, pre, (B, ks), generator=ctx.g, device=DEV)
     num = torch.randint(0, min(ks, cnt) + 1, (B,), generator=ctx.g, device=DEV).to(torch.int32)
     num[0] = min(ks, cnt)
+    opt = dict(ex)        # num: the counts (0, or more than keep_stride); bad_keep: entries -1 and pre_nms in image 0's list
+    if opt.get("num") is not None:
+        num = torch.tensor(opt["num"], device=DEV, dtype=torch.int32)
+    if opt.get("bad_keep"):
+        keep[0, 0], keep[0, ks - 1] = -1, pre
     out = _at(B * cnt * 4, al.get("proposals", 0)).view(B, cnt, 4)
     _call(name, I, {"dets": dets, "keep": keep, "num": num, "proposals": out})
     nrm = torch.tensor([I["norm_h"], I["norm_w"], I["norm_h"], I["norm_w"]], device=DEV, dtype=torch.float32)
     ref = torch.zeros(B, cnt, 4, device=DEV)
     for b in range(B):
-        k = int(num[b])
-        ref[b, :k] = dets[b, keep[b, :k], :4] / nrm
+        k = min(int(num[b]), ks, cnt)                        # a count past the list or the output reads neither
+        kk = keep[b, :k]
+        ok = (kk >= 0) & (kk < pre)                          # an entry that is no row of dets gives a row of zeros
+        ref[b, :k] = torch.where(ok[:, None], dets[b, kk.clamp(0, pre - 1), :4] / nrm, torch.zeros(k, 4, device=DEV))
     return _exact(out, ref, "%s %s" % (name, I))
 
 
