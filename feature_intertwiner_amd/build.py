@@ -67,6 +67,11 @@ HEAD16_HEADERS = CROP_DEV_HEADERS + ACT16_DEV_HEADERS + [os.path.join("..", ".."
 GRAD16_LIB_PATH = os.path.join(_HERE, "libfi_grad16.so")
 GRAD16_SOURCES = ["conv_grad16.hip", "conv_grad16_f16.hip"]
 GRAD16_HEADERS = ACT16_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_grad16.h")]
+# the data gradient with the producing layer's ReLU mask and column sums in its epilogue, for training on 16-bit
+# channels-last tensors (include/fi_train16.h): a twelfth library, built the same way
+TRAIN16_LIB_PATH = os.path.join(_HERE, "libfi_train16.so")
+TRAIN16_SOURCES = ["conv_train16.hip", "conv_train16_f16.hip"]
+TRAIN16_HEADERS = ACT16_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_train16.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
@@ -103,6 +108,7 @@ def _compile(sources, headers, force, verbose):
         deps += [os.path.join(CSRC, "head16_crop.hip")] if s.endswith("head16_crop_f16.hip") else []
         deps += [os.path.join(CSRC, "head16_out.hip")] if s.endswith("head16_out_f16.hip") else []
         deps += [os.path.join(CSRC, "conv_grad16.hip")] if s.endswith("conv_grad16_f16.hip") else []
+        deps += [os.path.join(CSRC, "conv_train16.hip")] if s.endswith("conv_train16_f16.hip") else []
         if force or _stale(o, deps):
             cmd = [HIPCC] + FLAGS + ["-c", s, "-o", o]
             if verbose:
@@ -114,7 +120,7 @@ def _compile(sources, headers, force, verbose):
 
 def build_hip(force=False, verbose=False):
     """Builds libfi_hip.so, libfi_eval.so, libfi_cocoeval.so, libfi_cocomask.so, libfi_ot.so, libfi_convt.so,
-    libfi_act16.so, libfi_pyr16.so, libfi_roi16.so, libfi_head16.so and libfi_grad16.so; returns the path of the first."""
+    libfi_act16.so, libfi_pyr16.so, libfi_roi16.so, libfi_head16.so, libfi_grad16.so and libfi_train16.so; returns the path of the first."""
     objs = _compile(SOURCES, HEADERS, force, verbose)
     if force or _stale(LIB_PATH, objs):
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
@@ -130,7 +136,8 @@ def build_hip(force=False, verbose=False):
                                   (PYR16_LIB_PATH, PYR16_SOURCES, PYR16_HEADERS),
                                   (ROI16_LIB_PATH, ROI16_SOURCES, ROI16_HEADERS),
                                   (HEAD16_LIB_PATH, HEAD16_SOURCES, HEAD16_HEADERS),
-                                  (GRAD16_LIB_PATH, GRAD16_SOURCES, GRAD16_HEADERS)):
+                                  (GRAD16_LIB_PATH, GRAD16_SOURCES, GRAD16_HEADERS),
+                                  (TRAIN16_LIB_PATH, TRAIN16_SOURCES, TRAIN16_HEADERS)):
         objs = _compile(sources, HEADERS + headers, force, verbose)
         if force or _stale(lib, objs + [LIB_PATH]):
             cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + [

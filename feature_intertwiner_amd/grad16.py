@@ -2,8 +2,9 @@
 csrc/conv_grad16.hip): the ReLU mask with its column sums, the data gradient and the weight gradient as thin wrappers,
 and `conv_bn_act16`, the differentiable form of act16.conv_bn_act16 for use WITH grad mode on.
 
-Step one of 16-bit training: the operators and one differentiable layer.  The model is not wired to it --
-MaskRCNN(mode='train') with a 16-bit MODEL.ACT_PRECISION keeps raising.  Which layers the kernels take is decided by
+Step one of 16-bit training: the operators and one differentiable layer.  The model is not wired to THIS layer --
+MaskRCNN(mode='train') with a 16-bit MODEL.ACT_PRECISION keeps raising; TRAIN.ACT_PRECISION runs the trunk on train16's
+layer, which calls the operators here.  Which layers the kernels take is decided by
 fi_grad16_eligible alone; nothing here restates its rules, and a layer it refuses is an error -- there is no fallback.
 """
 import ctypes

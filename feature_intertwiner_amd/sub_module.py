@@ -17,6 +17,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import act16 as _act16
+from . import train16 as _train16
 from . import conv as _conv
 from . import head16 as _head16
 from . import pyr16 as _pyr16
@@ -116,7 +117,34 @@ class Bottleneck(nn.Module):
         self.input_sole = False       # True: nothing but this block reads its input (the inner blocks of a stage)
         self.lateral_box = None       # set for ONE forward call by FPN.forward on the first block of C3..C5
 
+    def _forward_train16(self, x):
+        """The block on a 16-bit channels-last map that requires grad (TRAIN.ACT_PRECISION): the structure of the fp32
+        branches of forward() -- the same boxes, the same order of application -- on train16.conv_bn_act16."""
+        t16 = _train16.conv_bn_act16
+        box = GradBox()
+        if self.downsample is None:
+            # identity shortcut: conv3 leaves the shortcut's gradient in the box, conv1 adds it in its data-gradient
+            # epilogue and -- with `input_sole` -- applies the mask of the layer that produced x there too (Gate16)
+            out = t16(x, self.conv1, self.bn1, relu=True, dx_add_from=box, gate_dx=self.input_sole)
+            out = t16(out, self.conv2, self.bn2, relu=True, gate_dx=True)
+            return t16(out, self.conv3, self.bn3, relu=True, residual=x, res_grad_to=box, gate_dx=True)
+        # projection shortcut: applied after conv1, so its backward runs first and leaves its data gradient in the box.
+        # A lateral gradient (FPN.forward: the packed gradient of the unpacked map) is already in `lateral_box` then: it is
+        # chained as the projection's dx_add -- one more 16-bit rounding of it, no pass of its own -- and conv1, which now
+        # sees x's whole gradient, claims x's gate (stride 2: the cell form of the gated launch).  Without a lateral box
+        # (C2's first block reads the packed stem map: no gate there, the max-pool backward applies the stem's mask) conv1
+        # runs the ungated data gradient with dx_add.
+        lateral, self.lateral_box = self.lateral_box, None
+        if lateral is not None:
+            lateral.taker = True
+        out = t16(x, self.conv1, self.bn1, relu=True, dx_add_from=box, gate_dx=lateral is not None)
+        out = t16(out, self.conv2, self.bn2, relu=True, gate_dx=True)
+        residual = t16(x, self.downsample[0], self.downsample[1], relu=False, dx_give_to=box, dx_add_from=lateral)
+        return t16(out, self.conv3, self.bn3, relu=True, residual=residual, gate_dx=True)
+
     def forward(self, x):
+        if _act16.is_act16(x) and x.requires_grad and torch.is_grad_enabled():
+            return self._forward_train16(x)
         if _act16.is_act16(x):
             # a 16-bit channels-last map (MODEL.ACT_PRECISION, inference): every layer reads and writes one, the shortcut
             # is added in conv3's epilogue
@@ -244,10 +272,20 @@ class FPN(nn.Module):
                                           "(the 16-bit trunk is forward only: mode='inference')" % (act,))
         scope = _pyr16.act_scope(self.config.MODEL)     # all but 'trunk': p2..p6 stay 16-bit as well (_pyramid16)
         act = act != "fp32" and mode == 'inference' and x.is_cuda and not torch.is_grad_enabled()
+        # TRAIN.ACT_PRECISION 'bf16' / 'fp16': the trunk C2..C5 of a TRAIN step on 16-bit channels-last tensors (train16)
+        tact = _train16.act_precision(self.config)
+        train16 = tact != "fp32" and mode == 'train' and x.is_cuda and torch.is_grad_enabled()
         x = conv_bn_act(x, self.C1[0], self.C1[1], relu=True)       # C1 = conv, bn, relu, pad, maxpool
         x = _pad_maxpool(x, self.C1[3], self.C1[4])
         if act:
             x = _act16.pack(x, act_dtype)       # the pooled map, once; c2..c5 leave as fp32 NCHW (four launches)
+        elif train16:
+            if not x.requires_grad:
+                # the blocks take their training branch for a map that requires grad; a frozen stem gives none
+                raise _lib.FiError("TRAIN.ACT_PRECISION = %r needs a trainable stem: the pooled C1 map does not require grad "
+                                   "(every C1 parameter is frozen), so the 16-bit trunk would have no gradient to carry; "
+                                   "unfreeze the stem or leave TRAIN.ACT_PRECISION at 'fp32'" % (tact,))
+            x = _train16.pack(x, _act16.dtype_of(tact))      # differentiable: its backward unpacks the gradient
         # c2..c4 are read by the next stage AND by their lateral convolution: the lateral hands its data gradient to the
         # next stage's first block (GradBox; see Bottleneck.forward), which is the only one left talking to autograd
         fuse = mode == 'train' and not self.ot and x.is_cuda and torch.is_grad_enabled() and _conv.GATES
@@ -266,6 +304,12 @@ class FPN(nn.Module):
         if act:
             c = {lvl: _act16.unpack(m) for lvl, m in c.items()}
             c2 = c[2]
+        if train16:
+            # the laterals read fp32 NCHW maps; their data gradients come back through the unpack's backward, which packs
+            # them and leaves them in the next stage's lateral_box (when its first block took it) instead of the
+            # laterals giving fp32 tensors themselves
+            c = {lvl: _train16.unpack(m, boxes.get(lvl)) for lvl, m in c.items()}
+            c2, boxes = c[2], {}
         c3, c4, c5 = c[3], c[4], c[5]
         p5 = self.P5_conv1(c5)
         up = upsample2x
