@@ -72,6 +72,11 @@ GRAD16_HEADERS = ACT16_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_gr
 TRAIN16_LIB_PATH = os.path.join(_HERE, "libfi_train16.so")
 TRAIN16_SOURCES = ["conv_train16.hip", "conv_train16_f16.hip"]
 TRAIN16_HEADERS = ACT16_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_train16.h")]
+# the backward of the feature pyramid's top-down step on 16-bit channels-last tensors -- the 2 x 2 sum of the finer level's
+# gradient, the add and the column sums in one launch (include/fi_fpn16.h): a thirteenth library, built the same way
+FPN16_LIB_PATH = os.path.join(_HERE, "libfi_fpn16.so")
+FPN16_SOURCES = ["fpn16.hip", "fpn16_f16.hip"]
+FPN16_HEADERS = ACT16_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_fpn16.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
@@ -109,6 +114,7 @@ def _compile(sources, headers, force, verbose):
         deps += [os.path.join(CSRC, "head16_out.hip")] if s.endswith("head16_out_f16.hip") else []
         deps += [os.path.join(CSRC, "conv_grad16.hip")] if s.endswith("conv_grad16_f16.hip") else []
         deps += [os.path.join(CSRC, "conv_train16.hip")] if s.endswith("conv_train16_f16.hip") else []
+        deps += [os.path.join(CSRC, "fpn16.hip")] if s.endswith("fpn16_f16.hip") else []
         if force or _stale(o, deps):
             cmd = [HIPCC] + FLAGS + ["-c", s, "-o", o]
             if verbose:
@@ -120,7 +126,8 @@ def _compile(sources, headers, force, verbose):
 
 def build_hip(force=False, verbose=False):
     """Builds libfi_hip.so, libfi_eval.so, libfi_cocoeval.so, libfi_cocomask.so, libfi_ot.so, libfi_convt.so,
-    libfi_act16.so, libfi_pyr16.so, libfi_roi16.so, libfi_head16.so, libfi_grad16.so and libfi_train16.so; returns the path of the first."""
+    libfi_act16.so, libfi_pyr16.so, libfi_roi16.so, libfi_head16.so, libfi_grad16.so, libfi_train16.so and
+    libfi_fpn16.so; returns the path of the first."""
     objs = _compile(SOURCES, HEADERS, force, verbose)
     if force or _stale(LIB_PATH, objs):
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
@@ -137,7 +144,8 @@ def build_hip(force=False, verbose=False):
                                   (ROI16_LIB_PATH, ROI16_SOURCES, ROI16_HEADERS),
                                   (HEAD16_LIB_PATH, HEAD16_SOURCES, HEAD16_HEADERS),
                                   (GRAD16_LIB_PATH, GRAD16_SOURCES, GRAD16_HEADERS),
-                                  (TRAIN16_LIB_PATH, TRAIN16_SOURCES, TRAIN16_HEADERS)):
+                                  (TRAIN16_LIB_PATH, TRAIN16_SOURCES, TRAIN16_HEADERS),
+                                  (FPN16_LIB_PATH, FPN16_SOURCES, FPN16_HEADERS)):
         objs = _compile(sources, HEADERS + headers, force, verbose)
         if force or _stale(lib, objs + [LIB_PATH]):
             cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + [

@@ -11,6 +11,7 @@ from . import act16 as _act16
 from . import conv as _conv
 from . import pyr16 as _pyr16
 from . import train16 as _train16
+from . import fpn16 as _fpn16
 import os as _os
 # the mask head's batch whose results nothing reads runs on the second stream (same-box A/B 120.3 -> 117.2 ms/step)
 _DEAD_SIDE = _os.environ.get('FI_DEAD_SIDE', '1') != '0'
@@ -37,6 +38,7 @@ class MaskRCNN(nn.Module):
         self.config = config
         _pyr16.act_scope(config.MODEL)      # ValueError for a MODEL.ACT_SCOPE that its MODEL.ACT_PRECISION cannot carry
         _train16.check_config(config)       # ValueError for a bad TRAIN.ACT_PRECISION; 16-bit + FPN_OT_LOSS is not built
+        _fpn16.train_scope(config)          # ValueError for a TRAIN.ACT_SCOPE that its TRAIN.ACT_PRECISION cannot carry
         self._build(config)
         self._initialize_weights()
         self.feature_buffer = None

@@ -18,6 +18,7 @@ import torch.nn.functional as F
 from . import _lib
 from . import act16 as _act16
 from . import train16 as _train16
+from . import fpn16 as _fpn16
 from . import conv as _conv
 from . import head16 as _head16
 from . import pyr16 as _pyr16
@@ -275,6 +276,7 @@ class FPN(nn.Module):
         # TRAIN.ACT_PRECISION 'bf16' / 'fp16': the trunk C2..C5 of a TRAIN step on 16-bit channels-last tensors (train16)
         tact = _train16.act_precision(self.config)
         train16 = tact != "fp32" and mode == 'train' and x.is_cuda and torch.is_grad_enabled()
+        tscope = _fpn16.train_scope(self.config)        # 'pyramid': the laterals and smoothing layers too (_pyramid_train16)
         x = conv_bn_act(x, self.C1[0], self.C1[1], relu=True)       # C1 = conv, bn, relu, pad, maxpool
         x = _pad_maxpool(x, self.C1[3], self.C1[4])
         if act:
@@ -304,6 +306,8 @@ class FPN(nn.Module):
         if act:
             c = {lvl: _act16.unpack(m) for lvl, m in c.items()}
             c2 = c[2]
+        if train16 and tscope == "pyramid":
+            return self._pyramid_train16(c, boxes) + [ot_loss]
         if train16:
             # the laterals read fp32 NCHW maps; their data gradients come back through the unpack's backward, which packs
             # them and leaves them in the next stage's lateral_box (when its first block took it) instead of the
@@ -337,6 +341,23 @@ class FPN(nn.Module):
         p2 = self.P2_conv2(p2)
         p6 = self.P6(p5)
         return [p2, p3, p4, p5, p6, ot_loss]
+
+    def _pyramid_train16(self, c, boxes):
+        """[p2 .. p6] as fp32 NCHW tensors from the 16-bit c2..c5 of a TRAIN step (TRAIN.ACT_SCOPE = 'pyramid'): nothing is
+        unpacked in front of the laterals, p5pre..p2pre and the smoothed maps are 16-bit channels-last (fpn16), and only the
+        four smoothed maps are unpacked for the RPN's patch rows, the Dev stage and the heads -- that unpack's backward packs
+        their fp32 gradients.  Backward, with conv.GATES: each lateral leaves its g for the coarser layer in a GradBox (the
+        2 x 2 sum happens in that layer's own launch) and its data gradient in `boxes[l]`, the next trunk stage's
+        lateral_box; P5_conv1, c5's only reader, claims c5's gate."""
+        f16 = _fpn16
+        top = {lvl: GradBox() if _conv.GATES else None for lvl in (5, 4, 3)}      # level l takes what level l - 1 leaves
+        p5 = f16.conv_bias_act16(c[5], self.P5_conv1, gate_dx=True, top_grad_from=top[5])
+        p4 = f16.lateral16(c[4], self.P4_conv1, p5, top_grad_to=top[5], top_grad_from=top[4], dx_give_to=boxes.get(4))
+        p3 = f16.lateral16(c[3], self.P3_conv1, p4, top_grad_to=top[4], top_grad_from=top[3], dx_give_to=boxes.get(3))
+        p2 = f16.lateral16(c[2], self.P2_conv1, p3, top_grad_to=top[3], dx_give_to=boxes.get(2))
+        p5, p4, p3, p2 = (_train16.unpack(f16.conv_bias_act16(p, m[1])) for p, m in
+                          ((p5, self.P5_conv2), (p4, self.P4_conv2), (p3, self.P3_conv2), (p2, self.P2_conv2)))
+        return [p2, p3, p4, p5, self.P6(p5)]
 
     def _pyramid16(self, c):
         """[p2 .. p6] as 16-bit channels-last tensors from the 16-bit c2..c5 (MODEL.ACT_SCOPE 'pyramid' / 'roi', inference): nothing
