@@ -2,6 +2,9 @@
 // maps with even H and W for gfx950.  Reached from launch_wgrad (csrc/conv_igemm.hip) when plan_wgrad sets
 // FI_LAUNCH_WINOGRAD; it runs in the conv_wgrad_bm*_3x3 slot of the direct kernel and shares the slot's profiling counter.
 #include <stdint.h>
+#include <stdlib.h>
+
+#include <type_traits>
 
 #include "fi_common.h"
 
@@ -20,8 +23,8 @@ constexpr int kThreads = 256;
 // tile row, tile column) space, a whole number of stages of WG_STAGE tiles; a wavefront keeps the 16 transform-domain
 // accumulators of its 32 x 32 sub-block (256 registers: one wavefront per SIMD).  Per stage:
 //   Yt = A dY At and V = Bt d B are computed ONCE per workgroup on the way into LDS (a thread: one tile x one channel of
-//        each operand; x through 16 clamped 4-byte loads -- never an address outside x -- padding selected to zero
-//        afterwards, dy through two 8-byte loads), stored [tile][channel][position] with a channel pitch of 20 floats: a
+//        each operand; x through clamped loads, 4 x (4 + 8 + 4 bytes) -- never an address outside x -- padding selected
+//        to zero afterwards, dy through two 8-byte loads), stored [tile][channel][position] with a channel pitch of 20 floats: a
 //        lane's 16 A or B operands of one (channel, tile) are four conflict-free ds_read_b128.  The tile pitch is 8 floats
 //        more than 64 channels, so the ds_write_b128 of the 4 tiles x 2 channels of a lane group fall on distinct banks;
 //   v_mfma_f32_32x32x2_f32 takes two tiles (the half-wavefronts) of one position: 32 MFMAs per wavefront and stage.
@@ -30,6 +33,9 @@ constexpr int kThreads = 256;
 // stage and lost to the direct kernel on every 2-D map): the loads of stage s + 2 sit in the slots of stage s's first
 // tile pair, the transforms and LDS stores of stage s + 1 and the tile decode of stage s + 3 in the slots of the second.
 // An accumulator is one chain over the tiles of the split in order; the splits add with atomics.
+// A batch (fi::WgradBatch, by value) is several problems of one geometry in one launch: the flattened workgroup index is
+// (problem, split, block), and a problem takes fewer, longer splits than it would alone -- the 64 x 64 x 9 atomic adds of
+// a workgroup are paid per split.
 // The bias gradient is the sum of the dy values a thread stages (Cin block 0 only).
 // -------------------------------------------------------------------------------------
 constexpr int WG_B = fi::WINO_WG_BLOCK;
@@ -49,10 +55,21 @@ __device__ __forceinline__ int fast_div(int n, unsigned mul, unsigned sft)
     return mul ? (int)(__umulhi((unsigned)n, mul) >> sft) : n;
 }
 
+// BATCH: several problems of one geometry in one launch -- the workgroup order has the problem in front, (problem, pixel
+// split, block), so that a problem's operands stay in one L2, and x / dy / dw / dbias are taken from the by-value table (the
+// arguments are not read).  The plain kernel is its own instantiation, with no table among its arguments: the stage loop's
+// schedule is sensitive to everything around it, and a run-time `if (wb.n)` in ONE kernel cost the plain launches 10 %.
+// PAIR: the two centre columns of a window row (2 tx and 2 tx + 1: never clamped, 8-byte aligned -- x is 16-byte aligned, H
+// and W are even) come with ONE 8-byte load: 12 loads of x per thread and stage where the scalar staging has 16.  The values
+// staged and every floating-point operation are those of the scalar staging (PAIR = false, which FI_WINO_WGRAD_SCALAR_STAGING
+// keeps reachable): the results are the same bit for bit.
+struct NoBatch {};
+template <bool BATCH, bool PAIR>
 __global__ __launch_bounds__(kThreads, 1) void conv3x3_wino_wgrad_kernel(const float *__restrict__ x,
                                                                         const float *__restrict__ dy,
                                                                         float *__restrict__ dw,
-                                                                        float *__restrict__ dbias, WgGeom g)
+                                                                        float *__restrict__ dbias, WgGeom g,
+                                                                        typename std::conditional<BATCH, fi::WgradBatch, NoBatch>::type wb)
 {
     __shared__ __attribute__((aligned(16))) float Ys[2][WG_STAGE][WG_TP];     // A dY At [tile][cout][position]
     __shared__ __attribute__((aligned(16))) float Vs[2][WG_STAGE][WG_TP];     // Bt d B  [tile][cin][position]
@@ -60,10 +77,19 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_wino_wgrad_kernel(const f
     // XCD-aware order (1-D launch): the workgroups, sorted by (pixel split, block), are cut into 8 contiguous bands, one
     // per XCD -- the blocks of a split read the same dy / x ranges, so a split is fetched into ONE L2
     const int blocks = g.gx * g.gy;
-    const int nblk = blocks * g.splits;
+    int nblk = blocks * g.splits;                                    // workgroups of one problem
+    if constexpr (BATCH) nblk *= wb.n;
     const int per_xcd = (nblk + 7) >> 3;
-    const int idx = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    int idx = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
     if (idx >= nblk) return;
+    if constexpr (BATCH) {
+        const int prob = idx / (blocks * g.splits);
+        idx -= prob * blocks * g.splits;
+        x = wb.x[prob];
+        dy = wb.dy[prob];
+        dw = wb.dw[prob];
+        dbias = wb.db[prob];
+    }
     const int sp = idx / blocks, blk = idx - sp * blocks;
     const int by = blk / g.gx, bx = blk - by * g.gx;
     const int m0 = by * WG_B, c0 = bx * WG_B;
@@ -121,7 +147,15 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_wino_wgrad_kernel(const f
     };
     float raw[2][16];                             // the window, [row][column]
     float2 ry[2][2];                              // the dy tile, one row each
-    auto load_x = [&](int par, int r, int c) { raw[par][4 * r + c] = x[s_xo + s_ro[r] + s_co[c]]; };
+    auto load_x = [&](int par, int r, int c) {                       // (c is a constant wherever this is called)
+        if (PAIR && c == 1) {
+            const float2 v = *reinterpret_cast<const float2 *>(x + s_xo + s_ro[r] + s_co[1]);
+            raw[par][4 * r + 1] = v.x;
+            raw[par][4 * r + 2] = v.y;
+        } else if (!PAIR || c != 2) {
+            raw[par][4 * r + c] = x[s_xo + s_ro[r] + s_co[c]];
+        }
+    };
     auto load_y = [&](int par, int r) { ry[par][r] = *reinterpret_cast<const float2 *>(dy + s_yo + r * W); };
     float sd[4][4];                               // Bt d of the window being staged
     auto scol = [&](int par, int c) {
@@ -284,7 +318,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_wino_wgrad_kernel(const f
 
 namespace fi {
 
-void launch_conv3x3_wino_wgrad(const WinoWgradArgs &a, hipStream_t st)
+void launch_conv3x3_wino_wgrad(const WinoWgradArgs &a, hipStream_t st, const WgradBatch *batch)
 {
     WgGeom g;
     g.N = a.N; g.Cin = a.Cin; g.H = a.H; g.W = a.W; g.Cout = a.Cout;
@@ -296,9 +330,19 @@ void launch_conv3x3_wino_wgrad(const WinoWgradArgs &a, hipStream_t st)
     g.gy = a.Cout / WG_B;
     magic_div((unsigned)TT, g.mul_tt, g.sft_tt);
     magic_div((unsigned)TX, g.mul_tx, g.sft_tx);
-    const long nblk = (long)g.gx * g.gy * g.splits;
-    hipLaunchKernelGGL(conv3x3_wino_wgrad_kernel, dim3((unsigned)(((nblk + 7) / 8) * 8)), dim3(kThreads), 0, st, a.x, a.dy,
-                       a.dw, a.dbias, g);
+    const long nblk = (long)g.gx * g.gy * g.splits * (batch ? batch->n : 1);
+    const dim3 grid((unsigned)(((nblk + 7) / 8) * 8));
+    const dim3 block(kThreads);
+    // (the staging is no part of the plan: both instantiations run the planned launch and give the same bits; the switch is
+    // there for the probe and the tests)
+    const bool scalar_staging = getenv("FI_WINO_WGRAD_SCALAR_STAGING") != nullptr;
+    if (batch) {
+        auto k = scalar_staging ? conv3x3_wino_wgrad_kernel<true, false> : conv3x3_wino_wgrad_kernel<true, true>;
+        hipLaunchKernelGGL(k, grid, block, 0, st, a.x, a.dy, a.dw, a.dbias, g, *batch);
+    } else {
+        auto k = scalar_staging ? conv3x3_wino_wgrad_kernel<false, false> : conv3x3_wino_wgrad_kernel<false, true>;
+        hipLaunchKernelGGL(k, grid, block, 0, st, a.x, a.dy, a.dw, a.dbias, g, NoBatch{});
+    }
 }
 
 }  // namespace fi

@@ -82,16 +82,10 @@ struct ConvGeom {
                   // sums at dw + s * dw_slab (one writer per element: deterministic; the caller reduces the slabs)
 };
 
-// Several weight gradients of ONE geometry in one launch (fi_conv2d_weight_grad_batch): the operand pointers of every
-// problem travel by value in the kernel arguments -- no device-side table, no host-to-device copy per launch.
-constexpr int kWgBatchMax = FI_WGRAD_BATCH_MAX;
-struct WgradBatch {
-    int n;                                   // 0: a plain launch (the kernel's own x / dy / dw / dbias arguments)
-    const float *x[kWgBatchMax];
-    const float *dy[kWgBatchMax];
-    float *dw[kWgBatchMax];
-    float *db[kWgBatchMax];
-};
+// Several weight gradients of ONE geometry in one launch (fi_conv2d_weight_grad_batch): fi_common.h, which the Winograd form
+// of the 3x3 slot shares
+using fi::kWgBatchMax;
+using fi::WgradBatch;
 
 // Out-of-image taps of the tap-major gather read this instead of being masked after the load:
 // the loaded registers go to LDS untouched (no per-value select in the K loop).
@@ -1953,9 +1947,9 @@ void launch_wgrad_bm(const FiConvLaunch &l, ConvGeom g, const float *x, const fl
 void launch_wgrad(const FiConvLaunch &l, const ConvGeom &g, const float *x, const float *dy, float *dw, float *dbias,
                   hipStream_t st, const WgradBatch *batch = nullptr)
 {
-    if (l.flags & FI_LAUNCH_WINOGRAD) {          // conv3x3_wino_wgrad.hip (never a batch: plan_wgrad)
+    if (l.flags & FI_LAUNCH_WINOGRAD) {          // conv3x3_wino_wgrad.hip
         const fi::WinoWgradArgs a = {x, dy, dw, dbias, g.N, g.Cin, g.H, g.W, g.Cout, l.pixels_per_split / 4, l.splits};
-        fi::launch_conv3x3_wino_wgrad(a, st);
+        fi::launch_conv3x3_wino_wgrad(a, st, batch);
         return;
     }
     (l.tile_rows == 64 ? launch_wgrad_bm<64> : launch_wgrad_bm<128>)(l, g, x, dy, dw, dbias, st, batch);
@@ -2177,19 +2171,38 @@ void plan_wgrad(FiConvLaunch &l, const ConvGeom &g, int form, int nb, bool batch
     // Winograd F(2x2,3x3) form of the slot (conv3x3_wino_wgrad.hip: 16 MFMAs per 2 x 2 tile where the direct form needs 36):
     // a single FI_WGRAD_VEC problem -- same-size stride 1, tap-major, Cin % 128 == 0, operands aligned -- on a 3x3 / pad 1
     // window and a map with even H and W, from 256 input channels (every narrower layer keeps the direct kernel), Cout in
-    // whole blocks of the kernel.  A batch stays on the direct kernel's one launch.  FI_NO_WINOGRAD and
+    // whole blocks of the kernel.  A batch of nb > 1 problems takes the form too, in its one launch, when every problem has
+    // at least fi::WINO_WG_BATCH_MIN_TILES tiles (the C4 and C5 blocks; below that the direct kernel's one launch stays); a
+    // batch of one problem stays direct.  FI_NO_WINOGRAD and
     // FI_NO_WINOGRAD_WGRAD (both read per call) keep the direct form.  The launch keeps the slot's counter (kernel_id);
     // tile_rows, the grid, splits and pixels_per_split say what the Winograd kernel does: 64 x 64 blocks, and as many
     // splits of whole stages of tiles as fill fi::WINO_WG_SLOTS workgroups (one round of the CUs), none under
-    // fi::WINO_WG_MIN_TILES tiles.
-    if (form == FI_WGRAD_VEC && !gemm && !batched && nb == 1 && g.R == 3 && g.S == 3 && g.ph == 1 && g.pw == 1 &&
-        g.H % 2 == 0 && g.W % 2 == 0 && g.Cin >= 256 && Cout % fi::WINO_WG_BLOCK == 0 && !getenv("FI_NO_WINOGRAD") &&
-        !getenv("FI_NO_WINOGRAD_WGRAD")) {
-        const int ntiles = g.N * (g.H / 2) * (g.W / 2);
+    // fi::WINO_WG_MIN_TILES tiles.  A batch fills the slots together: per problem, the split count that minimises rounds of
+    // the slots x (tiles per split + the fixed cost of a workgroup, fi::WINO_WG_FIXED_TILES).
+    const int wino_tiles = g.N * (g.H / 2) * (g.W / 2);
+    const bool wino_batch = batched && nb > 1 && wino_tiles >= fi::WINO_WG_BATCH_MIN_TILES;
+    if (form == FI_WGRAD_VEC && !gemm && ((!batched && nb == 1) || wino_batch) && g.R == 3 && g.S == 3 && g.ph == 1 &&
+        g.pw == 1 && g.H % 2 == 0 && g.W % 2 == 0 && g.Cin >= 256 && Cout % fi::WINO_WG_BLOCK == 0 &&
+        !getenv("FI_NO_WINOGRAD") && !getenv("FI_NO_WINOGRAD_WGRAD")) {
+        const int ntiles = wino_tiles;
         const int blocks = (g.Cin / fi::WINO_WG_BLOCK) * (Cout / fi::WINO_WG_BLOCK);
         const int max_sp = fi::ceil_div(ntiles, fi::WINO_WG_MIN_TILES);
         const int want_sp = fi::WINO_WG_SLOTS / blocks;
-        const int sp = want_sp < 1 ? 1 : (want_sp > max_sp ? max_sp : want_sp);
+        int sp = want_sp < 1 ? 1 : (want_sp > max_sp ? max_sp : want_sp);
+        if (wino_batch) {
+            long best_cost = -1;
+            for (int s = 1; s <= max_sp && s <= 64; ++s) {
+                const int t = fi::ceil_div(fi::ceil_div(ntiles, s), fi::WINO_WG_STAGE) * fi::WINO_WG_STAGE;
+                if (s > 1 && t < fi::WINO_WG_MIN_TILES) break;
+                const long total = (long)blocks * nb * fi::ceil_div(ntiles, t);
+                const long rounds = (total + fi::WINO_WG_SLOTS - 1) / fi::WINO_WG_SLOTS;
+                const long cost = rounds * (t + fi::WINO_WG_FIXED_TILES);
+                if (best_cost < 0 || cost < best_cost) {
+                    best_cost = cost;
+                    sp = s;
+                }
+            }
+        }
         const int tps = fi::ceil_div(fi::ceil_div(ntiles, sp), fi::WINO_WG_STAGE) * fi::WINO_WG_STAGE;
         l.flags = (l.flags & ~FI_LAUNCH_ROW_UNIFORM) | FI_LAUNCH_WINOGRAD | FI_LAUNCH_SWIZZLED;
         l.tile_rows = fi::WINO_WG_BLOCK;

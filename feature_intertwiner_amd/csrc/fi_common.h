@@ -49,13 +49,33 @@ constexpr int WINO_WG_BLOCK = 64;    // a workgroup's Cout and Cin block (Cin an
 constexpr int WINO_WG_STAGE = 4;     // 2 x 2 tiles per LDS stage; a pixel split is a whole number of stages
 constexpr int WINO_WG_SLOTS = 256;   // workgroups blocks x splits may reach: one per CU (82 KB of LDS, 512 registers per lane)
 constexpr int WINO_WG_MIN_TILES = 32;     // fewest tiles of a split (8 stages) unless it is the only one
+// A batch (fi_conv2d_weight_grad_batch) takes the kernel from this many tiles per problem; its splits minimise
+// rounds of WINO_WG_SLOTS workgroups x (tiles per split + WINO_WG_FIXED_TILES)
+constexpr int WINO_WG_BATCH_MIN_TILES = 1024;
+// a workgroup's prologue and atomic epilogue in tiles of the stage loop: profiles/wino_wgrad_probe.txt, 256 -> 256 on N4 maps,
+// 133.1 us at 256 tiles per split (64 x 64) and 428.6 us at 1024 (128 x 128): 0.385 us per tile, 35 us fixed = 90 tiles; a
+// round of the C4 x12 batch (1024 tiles) takes 434 us, 40 us above its tiles
+constexpr int WINO_WG_FIXED_TILES = 96;
 struct WinoWgradArgs {
     const float *x, *dy;
     float *dw, *dbias;               // dbias may be null
     int N, Cin, H, W, Cout;
-    int tiles_per_split, splits;     // the plan's cut of the N * H/2 * W/2 tiles
+    int tiles_per_split, splits;     // the plan's cut of the N * H/2 * W/2 tiles (a batch: of every problem)
 };
-void launch_conv3x3_wino_wgrad(const WinoWgradArgs &a, hipStream_t st);
+
+// Several weight gradients of ONE geometry in one launch (fi_conv2d_weight_grad_batch): the operand pointers of every
+// problem travel by value in the kernel arguments -- no device-side table, no host-to-device copy per launch.
+constexpr int kWgBatchMax = FI_WGRAD_BATCH_MAX;
+struct WgradBatch {
+    int n;                                   // 0: a plain launch (the kernel's own x / dy / dw / dbias arguments)
+    const float *x[kWgBatchMax];
+    const float *dy[kWgBatchMax];
+    float *dw[kWgBatchMax];
+    float *db[kWgBatchMax];
+};
+// batch: null, or the problems of one launch (a.x / a.dy / a.dw / a.dbias are then not read).  FI_WINO_WGRAD_SCALAR_STAGING
+// in the environment, read per call, takes the instantiation that stages with 4-byte loads only (the same results)
+void launch_conv3x3_wino_wgrad(const WinoWgradArgs &a, hipStream_t st, const WgradBatch *batch = nullptr);
 
 // n / d == umulhi(n, mul) >> sft for 0 <= n < 2^31 (mul = ceil(2^(32+sft) / d), 32 + sft = 31 + ceil(log2 d)); mul == 0
 // encodes d == 1

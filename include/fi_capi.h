@@ -518,12 +518,19 @@ int fi_gemm_nt_plan(const float *a, const float *b, const float *scale, const fl
  *   SWIZZLED     FI_WGRAD_VEC with at least 32768 pixels (unless FI_NO_WG_SWZ is set) or with a batch: a 1-D grid of
  *                grid_x * grid_y * grid_z * per_launch workgroups rounded up to a multiple of 8; grid_x/y/z stay the logical
  *                grid (column tiles, Cout tiles, pixel splits)
- *   WINOGRAD     one FI_WGRAD_VEC problem (never a batch) on a 3x3 / pad 1 window and a map with even H and W, Cin >= 256,
+ *   WINOGRAD     one FI_WGRAD_VEC problem on a 3x3 / pad 1 window and a map with even H and W, Cin >= 256,
  *                Cout % 64 == 0: conv3x3_wino_wgrad_kernel in the slot (kernel_id) of the direct kernel.  tile_rows 64;
  *                grid_x / grid_y the 64-channel blocks of Cin / Cout; the splits are whole stages of 4 tiles of 2 x 2
  *                pixels (pixels_per_split = 4 x the tiles of a split), as many as fill 256 workgroups, none under 32
- *                tiles (WINO_WG_SLOTS / WINO_WG_MIN_TILES in csrc/fi_common.h); always SWIZZLED, never ROW_UNIFORM.  FI_NO_WINOGRAD or FI_NO_WINOGRAD_WGRAD in the environment,
- *                read per call, keep the direct kernel
+ *                tiles (WINO_WG_SLOTS / WINO_WG_MIN_TILES in csrc/fi_common.h); always SWIZZLED, never ROW_UNIFORM.
+ *                A batch of per_launch > 1 problems takes the form under the same conditions when every problem has at
+ *                least 1024 tiles of 2 x 2 pixels (WINO_WG_BATCH_MIN_TILES; a smaller one keeps the direct kernel's one
+ *                launch): one launch of per_launch x grid_x x grid_y x splits workgroups, splits / pixels_per_split those
+ *                of EACH problem -- the count that minimises rounds of 256 workgroups x (tiles of a split + 96, the fixed
+ *                cost of a workgroup: WINO_WG_FIXED_TILES), none under 32 tiles.  FI_NO_WINOGRAD or
+ *                FI_NO_WINOGRAD_WGRAD in the environment, read per call, keep the direct kernel (the direct batch);
+ *                FI_WINO_WGRAD_SCALAR_STAGING, read per call, keeps the Winograd kernel's staging with 4-byte loads
+ *                only (the same results bit for bit; the plan does not change)
  *   tile_rows, splits, pixels_per_split   see fi_conv2d_weight_grad_split_plan; per_launch see fi_conv2d_weight_grad_plan */
 enum {
     FI_FWD_GENERIC = 0,
