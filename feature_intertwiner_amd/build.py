@@ -77,6 +77,12 @@ TRAIN16_HEADERS = ACT16_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_t
 FPN16_LIB_PATH = os.path.join(_HERE, "libfi_fpn16.so")
 FPN16_SOURCES = ["fpn16.hip", "fpn16_f16.hip"]
 FPN16_HEADERS = ACT16_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_fpn16.h")]
+# what keeps a train step's pyramid 16-bit up to the RoI crops -- the RPN's patch rows gathered from and scattered into
+# 16-bit maps, the masked pack of RoIAlign's fp32 gradient with column sums (include/fi_crops16.h): a fourteenth library,
+# built the same way
+CROPS16_LIB_PATH = os.path.join(_HERE, "libfi_crops16.so")
+CROPS16_SOURCES = ["crops16.hip", "crops16_f16.hip"]
+CROPS16_HEADERS = ACT16_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_crops16.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
@@ -115,6 +121,7 @@ def _compile(sources, headers, force, verbose):
         deps += [os.path.join(CSRC, "conv_grad16.hip")] if s.endswith("conv_grad16_f16.hip") else []
         deps += [os.path.join(CSRC, "conv_train16.hip")] if s.endswith("conv_train16_f16.hip") else []
         deps += [os.path.join(CSRC, "fpn16.hip")] if s.endswith("fpn16_f16.hip") else []
+        deps += [os.path.join(CSRC, "crops16.hip")] if s.endswith("crops16_f16.hip") else []
         if force or _stale(o, deps):
             cmd = [HIPCC] + FLAGS + ["-c", s, "-o", o]
             if verbose:
@@ -126,8 +133,8 @@ def _compile(sources, headers, force, verbose):
 
 def build_hip(force=False, verbose=False):
     """Builds libfi_hip.so, libfi_eval.so, libfi_cocoeval.so, libfi_cocomask.so, libfi_ot.so, libfi_convt.so,
-    libfi_act16.so, libfi_pyr16.so, libfi_roi16.so, libfi_head16.so, libfi_grad16.so, libfi_train16.so and
-    libfi_fpn16.so; returns the path of the first."""
+    libfi_act16.so, libfi_pyr16.so, libfi_roi16.so, libfi_head16.so, libfi_grad16.so, libfi_train16.so,
+    libfi_fpn16.so and libfi_crops16.so; returns the path of the first."""
     objs = _compile(SOURCES, HEADERS, force, verbose)
     if force or _stale(LIB_PATH, objs):
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
@@ -145,7 +152,8 @@ def build_hip(force=False, verbose=False):
                                   (HEAD16_LIB_PATH, HEAD16_SOURCES, HEAD16_HEADERS),
                                   (GRAD16_LIB_PATH, GRAD16_SOURCES, GRAD16_HEADERS),
                                   (TRAIN16_LIB_PATH, TRAIN16_SOURCES, TRAIN16_HEADERS),
-                                  (FPN16_LIB_PATH, FPN16_SOURCES, FPN16_HEADERS)):
+                                  (FPN16_LIB_PATH, FPN16_SOURCES, FPN16_HEADERS),
+                                  (CROPS16_LIB_PATH, CROPS16_SOURCES, CROPS16_HEADERS)):
         objs = _compile(sources, HEADERS + headers, force, verbose)
         if force or _stale(lib, objs + [LIB_PATH]):
             cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + [

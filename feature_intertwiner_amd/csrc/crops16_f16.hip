@@ -1,0 +1,4 @@
+// crops16_f16.hip -- the kernels of crops16.hip on IEEE half tensors: fi_crops16_*_f16.  Same grids, same lane maps, same
+// sums; only the 16-bit type differs (an overflow rounds to infinity, as IEEE says).
+#define FI_E16_HALF 1
+#include "crops16.hip"

@@ -12,6 +12,7 @@ from . import conv as _conv
 from . import pyr16 as _pyr16
 from . import train16 as _train16
 from . import fpn16 as _fpn16
+from . import crops16 as _crops16
 import os as _os
 # the mask head's batch whose results nothing reads runs on the second stream (same-box A/B 120.3 -> 117.2 ms/step)
 _DEAD_SIDE = _os.environ.get('FI_DEAD_SIDE', '1') != '0'
@@ -39,6 +40,7 @@ class MaskRCNN(nn.Module):
         _pyr16.act_scope(config.MODEL)      # ValueError for a MODEL.ACT_SCOPE that its MODEL.ACT_PRECISION cannot carry
         _train16.check_config(config)       # ValueError for a bad TRAIN.ACT_PRECISION; 16-bit + FPN_OT_LOSS is not built
         _fpn16.train_scope(config)          # ValueError for a TRAIN.ACT_SCOPE that its TRAIN.ACT_PRECISION cannot carry
+        _crops16.check_config(config)       # NotImplementedError for what TRAIN.ACT_SCOPE = 'crops' cannot carry
         self._build(config)
         self._initialize_weights()
         self.feature_buffer = None
@@ -159,8 +161,13 @@ class MaskRCNN(nn.Module):
             for b_ in to_rpn:
                 if b_ is not None:
                     b_.taker = True                     # _PatchRowsFn takes what the make-up layer leaves
-            row_logits, row_bbox = self.rpn.forward_rows(rpn_maps, r_img, r_anchor, r_valid,
-                                                         grad_boxes=list(to_rpn) + [None] * (len(rpn_maps) - len(to_rpn)))
+            # TRAIN.ACT_SCOPE 'crops' (16-bit p2..p6): p6 is p5's stride-2 subsample -- the rows read it as p5 with step 2
+            # and their backward adds into p5's gradient
+            crops16 = _act16.is_act16(p2)
+            row_logits, row_bbox = self.rpn.forward_rows([p2, p3, p4, p5, p5] if crops16 else rpn_maps, r_img, r_anchor,
+                                                         r_valid,
+                                                         grad_boxes=list(to_rpn) + [None] * (len(rpn_maps) - len(to_rpn)),
+                                                         steps=[1, 1, 1, 1, 2] if crops16 else None)
         else:
             outs = [self.rpn(p, to_rpn[i] if i < len(to_rpn) else None) for i, p in enumerate(rpn_maps)]
         rpn_logits, rpn_probs, rpn_bbox = [torch.cat(list(o), dim=1) for o in zip(*outs)]

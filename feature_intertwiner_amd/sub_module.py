@@ -19,6 +19,7 @@ from . import _lib
 from . import act16 as _act16
 from . import train16 as _train16
 from . import fpn16 as _fpn16
+from . import crops16 as _crops16
 from . import conv as _conv
 from . import head16 as _head16
 from . import pyr16 as _pyr16
@@ -276,7 +277,10 @@ class FPN(nn.Module):
         # TRAIN.ACT_PRECISION 'bf16' / 'fp16': the trunk C2..C5 of a TRAIN step on 16-bit channels-last tensors (train16)
         tact = _train16.act_precision(self.config)
         train16 = tact != "fp32" and mode == 'train' and x.is_cuda and torch.is_grad_enabled()
-        tscope = _fpn16.train_scope(self.config)        # 'pyramid': the laterals and smoothing layers too (_pyramid_train16)
+        # 'pyramid': the laterals and smoothing layers too (_pyramid_train16); 'crops': p2..p5 stay 16-bit behind them
+        tscope = _fpn16.train_scope(self.config)
+        if train16 and tscope == "crops":
+            _crops16.require_gates()
         x = conv_bn_act(x, self.C1[0], self.C1[1], relu=True)       # C1 = conv, bn, relu, pad, maxpool
         x = _pad_maxpool(x, self.C1[3], self.C1[4])
         if act:
@@ -306,8 +310,8 @@ class FPN(nn.Module):
         if act:
             c = {lvl: _act16.unpack(m) for lvl, m in c.items()}
             c2 = c[2]
-        if train16 and tscope == "pyramid":
-            return self._pyramid_train16(c, boxes) + [ot_loss]
+        if train16 and tscope in ("pyramid", "crops"):
+            return self._pyramid_train16(c, boxes, keep16=tscope == "crops") + [ot_loss]
         if train16:
             # the laterals read fp32 NCHW maps; their data gradients come back through the unpack's backward, which packs
             # them and leaves them in the next stage's lateral_box (when its first block took it) instead of the
@@ -342,21 +346,28 @@ class FPN(nn.Module):
         p6 = self.P6(p5)
         return [p2, p3, p4, p5, p6, ot_loss]
 
-    def _pyramid_train16(self, c, boxes):
+    def _pyramid_train16(self, c, boxes, keep16=False):
         """[p2 .. p6] as fp32 NCHW tensors from the 16-bit c2..c5 of a TRAIN step (TRAIN.ACT_SCOPE = 'pyramid'): nothing is
         unpacked in front of the laterals, p5pre..p2pre and the smoothed maps are 16-bit channels-last (fpn16), and only the
         four smoothed maps are unpacked for the RPN's patch rows, the Dev stage and the heads -- that unpack's backward packs
         their fp32 gradients.  Backward, with conv.GATES: each lateral leaves its g for the coarser layer in a GradBox (the
         2 x 2 sum happens in that layer's own launch) and its data gradient in `boxes[l]`, the next trunk stage's
-        lateral_box; P5_conv1, c5's only reader, claims c5's gate."""
+        lateral_box; P5_conv1, c5's only reader, claims c5's gate.
+        keep16 (TRAIN.ACT_SCOPE = 'crops'): the four smoothed maps are RETURNED 16-bit channels-last -- no unpack runs, their
+        readers (crops16) hand back 16-bit gradients -- and p6 is the stride-2 subsample of p5, made without a graph: its
+        only reader with a gradient, the RPN's patch rows, adds into p5's gradient at the even pixels."""
         f16 = _fpn16
         top = {lvl: GradBox() if _conv.GATES else None for lvl in (5, 4, 3)}      # level l takes what level l - 1 leaves
         p5 = f16.conv_bias_act16(c[5], self.P5_conv1, gate_dx=True, top_grad_from=top[5])
         p4 = f16.lateral16(c[4], self.P4_conv1, p5, top_grad_to=top[5], top_grad_from=top[4], dx_give_to=boxes.get(4))
         p3 = f16.lateral16(c[3], self.P3_conv1, p4, top_grad_to=top[4], top_grad_from=top[3], dx_give_to=boxes.get(3))
         p2 = f16.lateral16(c[2], self.P2_conv1, p3, top_grad_to=top[3], dx_give_to=boxes.get(2))
-        p5, p4, p3, p2 = (_train16.unpack(f16.conv_bias_act16(p, m[1])) for p, m in
+        p5, p4, p3, p2 = (f16.conv_bias_act16(p, m[1]) for p, m in
                           ((p5, self.P5_conv2), (p4, self.P4_conv2), (p3, self.P3_conv2), (p2, self.P2_conv2)))
+        if keep16:
+            p6 = p5.detach()[:, :, ::2, ::2].contiguous(memory_format=torch.channels_last)      # MaxPool2d(1, 2)
+            return [p2, p3, p4, p5, p6]
+        p5, p4, p3, p2 = (_train16.unpack(p) for p in (p5, p4, p3, p2))
         return [p2, p3, p4, p5, self.P6(p5)]
 
     def _pyramid16(self, c):
@@ -508,7 +519,7 @@ class RPN(nn.Module):
             base += n
         return out
 
-    def forward_rows(self, maps, image, anchor, valid, grad_boxes=None):
+    def forward_rows(self, maps, image, anchor, valid, grad_boxes=None, steps=None):
         """The RPN's outputs at SELECTED anchors only: (logits [R, 2], bbox [R, 4]) for rows (image[r], anchor[r]) of the
         level-major anchor list (lib/layers.py:41-44), zeros where valid[r] is False.
 
@@ -518,11 +529,17 @@ class RPN(nn.Module):
         (under no_grad: the proposal layer needs every anchor's score); for the losses the same two layers are evaluated
         on the selected pixels' 3 x 3 patches as matrix products (conv.linear: [R, 9*256] . W_shared^T -> ReLU -> . W_heads^T),
         whose backward IS the convolution's backward restricted to the rows that have a gradient; the patch gather's
-        backward scatters the input gradient into the level maps (_PatchRowsFn)."""
+        backward scatters the input gradient into the level maps (_PatchRowsFn).
+        16-bit channels-last maps (TRAIN.ACT_SCOPE = 'crops'): the patches are gathered from them by crops16.patch_rows16
+        -- the rows stay fp32, widening is exact -- whose backward adds into the 16-bit gradients the boxes hold; `steps`
+        are its per-level strides (the last level as the tensor before it with step 2)."""
         assert self.anchor_stride == 1, "row form: stride-1 RPN only"
         per_loc = self.conv_class.weight.shape[0] // 2
         rows_image = torch.where(valid, image, torch.full_like(image, -1))
-        patches = _PatchRowsFn.apply(rows_image, anchor.clamp(min=0), per_loc, grad_boxes, *maps)
+        if _act16.is_act16(maps[0]):
+            patches = _crops16.patch_rows16(maps, rows_image, anchor.clamp(min=0), per_loc, grad_boxes, steps)
+        else:
+            patches = _PatchRowsFn.apply(rows_image, anchor.clamp(min=0), per_loc, grad_boxes, *maps)
         k = anchor.clamp(min=0) % per_loc          # every level's first anchor index is a multiple of per_loc
         a = anchor
         cs = self.conv_shared
@@ -570,6 +587,7 @@ class Dev(nn.Module):
         self.roi_spatial_scale = [1. / 4, 1. / 8, 1. / 16, 1. / 32]
         if _pyr16.act_scope(config.MODEL) in ('roi', 'detect'):
             self._require_roi16()
+        _crops16.check_config(config)       # TRAIN.ACT_SCOPE = 'crops': what the 16-bit route to the crops cannot carry
         if self.use_dev:
             self.feat_pool_size = config.DEV.FEAT_BRANCH_POOL_SIZE
             assert self.feat_pool_size % 2 == 0, 'pool size of feature branch has to be even'
@@ -675,6 +693,14 @@ class Dev(nn.Module):
             # out (a training-mode BatchNorm raises in conv_bn_act16)
             self._require_roi16()
             seqs = [self.upsample[i if cfg.DEV.MULTI_UPSAMPLER else 0] for i in range(len(x))]
+            if torch.is_grad_enabled() and x[0].requires_grad:
+                # TRAIN.ACT_SCOPE 'crops': the same launch with a graph.  The outputs carry a Gate16 for the crops to claim;
+                # the data gradient goes to give_to's taker (the RPN's patch rows).  The raw maps' big-box crop builds no
+                # graph under this scope (Dev.__init__ refuses the settings that need one): nothing to take
+                give = [give_to[i] if (give_to and give_to[i] is not None and give_to[i].taker) else None
+                        for i in range(len(x))]
+                return [_train16.conv_bn_act16(m, seq[0], seq[1], relu=True, dx_give_to=b)
+                        for m, seq, b in zip(x, seqs, give)]
             return [_act16.conv_bn_act16(m, seq[0], seq[1], relu=True) for m, seq in zip(x, seqs)]
 
         def make_up(i, m):
@@ -773,13 +799,22 @@ class Dev(nn.Module):
         if not static:
             n2, n3, n4, n5 = (int(v) for v in counts_ready().tolist())
         group = CropGradGroup()      # both crops' gradients accumulate in ONE set of buffers (no add pass per level)
-        pooled = self._crop(up_maps, boxes, box_ind, level, self.pool_size, group)
-        if front:
-            perm, inv = self._front_permutation(bs, R, front, rois.device)
-            mask_and_feat = self._crop(up_maps, boxes[perm], box_ind[perm], level[perm], self.mask_pool_size, group)
+        if _act16.is_act16(up_maps[0]) and torch.is_grad_enabled() and up_maps[0].requires_grad:
+            # TRAIN.ACT_SCOPE 'crops': both crops are ONE autograd node (crops16.pyramid_crops16) that returns 16-bit map
+            # gradients, masked for the make-up layer
+            self._require_roi16()
+            perm, inv = self._front_permutation(bs, R, front, rois.device) if front else (None, None)
+            mask_spec = (boxes[perm], box_ind[perm], level[perm]) if front else (boxes, box_ind, level)
+            pooled, mask_and_feat = _crops16.pyramid_crops16(up_maps, [(boxes, box_ind, level, self.pool_size),
+                                                                       mask_spec + (self.mask_pool_size,)])
         else:
-            inv = None
-            mask_and_feat = self._crop(up_maps, boxes, box_ind, level, self.mask_pool_size, group)
+            pooled = self._crop(up_maps, boxes, box_ind, level, self.pool_size, group)
+            if front:
+                perm, inv = self._front_permutation(bs, R, front, rois.device)
+                mask_and_feat = self._crop(up_maps, boxes[perm], box_ind[perm], level[perm], self.mask_pool_size, group)
+            else:
+                inv = None
+                mask_and_feat = self._crop(up_maps, boxes, box_ind, level, self.mask_pool_size, group)
         if cfg.DEV.BASELINE:
             return pooled, mask_and_feat, []
 
