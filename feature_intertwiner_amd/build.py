@@ -83,6 +83,12 @@ FPN16_HEADERS = ACT16_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_fpn
 CROPS16_LIB_PATH = os.path.join(_HERE, "libfi_crops16.so")
 CROPS16_SOURCES = ["crops16.hip", "crops16_f16.hip"]
 CROPS16_HEADERS = ACT16_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_crops16.h")]
+# what lets a train step run its box and mask heads on 16-bit channels-last crops -- RoIAlign's backward from 16-bit crop
+# gradients, the backward of the mask head's class-selected output layer (include/fi_heads16.h): a fifteenth library, built
+# the same way
+HEADS16_LIB_PATH = os.path.join(_HERE, "libfi_heads16.so")
+HEADS16_SOURCES = ["heads16.hip", "heads16_f16.hip"]
+HEADS16_HEADERS = CROP_DEV_HEADERS + ACT16_DEV_HEADERS + [os.path.join("..", "..", "include", "fi_heads16.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
@@ -122,6 +128,7 @@ def _compile(sources, headers, force, verbose):
         deps += [os.path.join(CSRC, "conv_train16.hip")] if s.endswith("conv_train16_f16.hip") else []
         deps += [os.path.join(CSRC, "fpn16.hip")] if s.endswith("fpn16_f16.hip") else []
         deps += [os.path.join(CSRC, "crops16.hip")] if s.endswith("crops16_f16.hip") else []
+        deps += [os.path.join(CSRC, "heads16.hip")] if s.endswith("heads16_f16.hip") else []
         if force or _stale(o, deps):
             cmd = [HIPCC] + FLAGS + ["-c", s, "-o", o]
             if verbose:
@@ -134,7 +141,7 @@ def _compile(sources, headers, force, verbose):
 def build_hip(force=False, verbose=False):
     """Builds libfi_hip.so, libfi_eval.so, libfi_cocoeval.so, libfi_cocomask.so, libfi_ot.so, libfi_convt.so,
     libfi_act16.so, libfi_pyr16.so, libfi_roi16.so, libfi_head16.so, libfi_grad16.so, libfi_train16.so,
-    libfi_fpn16.so and libfi_crops16.so; returns the path of the first."""
+    libfi_fpn16.so, libfi_crops16.so and libfi_heads16.so; returns the path of the first."""
     objs = _compile(SOURCES, HEADERS, force, verbose)
     if force or _stale(LIB_PATH, objs):
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
@@ -153,7 +160,8 @@ def build_hip(force=False, verbose=False):
                                   (GRAD16_LIB_PATH, GRAD16_SOURCES, GRAD16_HEADERS),
                                   (TRAIN16_LIB_PATH, TRAIN16_SOURCES, TRAIN16_HEADERS),
                                   (FPN16_LIB_PATH, FPN16_SOURCES, FPN16_HEADERS),
-                                  (CROPS16_LIB_PATH, CROPS16_SOURCES, CROPS16_HEADERS)):
+                                  (CROPS16_LIB_PATH, CROPS16_SOURCES, CROPS16_HEADERS),
+                                  (HEADS16_LIB_PATH, HEADS16_SOURCES, HEADS16_HEADERS)):
         objs = _compile(sources, HEADERS + headers, force, verbose)
         if force or _stale(lib, objs + [LIB_PATH]):
             cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + [

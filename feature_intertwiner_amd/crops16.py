@@ -79,6 +79,14 @@ def check_config(config):
     configuration the 16-bit route to the crops cannot carry.  Any other scope: nothing to check."""
     if fpn16.train_scope(config) != SCOPE:
         return
+    why = unsupported(config)
+    if why is not None:
+        raise NotImplementedError("TRAIN.ACT_SCOPE = 'crops' needs " + why)
+
+
+def unsupported(config):
+    """What the 16-bit route to the crops cannot carry in `config`, as the text behind "TRAIN.ACT_SCOPE = ... needs ", or
+    None: the one list of check_config, which heads16.check_config shares."""
     dev, why = config.DEV, None
     if not dev.SWITCH:
         why = "DEV.SWITCH = True (got False): without the Dev stage there is no make-up layer in front of the crops"
@@ -94,14 +102,13 @@ def check_config(config):
               % (config.RPN.ANCHOR_STRIDE,)
     elif getattr(config.TRAIN, "FPN_OT_LOSS", False):
         why = "TRAIN.FPN_OT_LOSS = False: the optimal-transport branch of the pyramid reads fp32 maps"
-    if why is not None:
-        raise NotImplementedError("TRAIN.ACT_SCOPE = 'crops' needs " + why)
+    return why
 
 
-def require_gates():
+def require_gates(scope=SCOPE):
     """The refusal at the call: with conv.GATES off the dense RPN builds a graph, and that has no 16-bit form."""
     if not _conv.GATES:
-        raise _lib.FiError("TRAIN.ACT_SCOPE = 'crops' needs conv.GATES on: the dense RPN with a graph and the gradient "
+        raise _lib.FiError("TRAIN.ACT_SCOPE = %r needs conv.GATES on" % (scope,) + ": the dense RPN with a graph and the gradient "
                            "hand-offs through autograd have no 16-bit form; there is no fallback")
 
 

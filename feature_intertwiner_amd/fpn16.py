@@ -34,7 +34,7 @@ SIGNATURES = {
     "fi_fpn16_topdown_grad_bf16": _TOPDOWN,
     "fi_fpn16_topdown_grad_f16": _TOPDOWN,
 }
-SCOPES = ("trunk", "pyramid", "crops")
+SCOPES = ("trunk", "pyramid", "crops", "heads")
 _BIAS_ONLY = "bias-only"          # where grad16.weight_t16 keeps the key of a BatchNorm fold (a tuple): no fold, scale 1
 _fpn16 = None
 _STATS = {"topdown": 0, "sums": 0, "lateral": 0, "conv": 0, "top_to_autograd": 0, "weights": 0}
@@ -74,13 +74,14 @@ def reset_stats():
 def train_scope(config):
     """config.TRAIN.ACT_SCOPE: 'trunk' (also when absent: the 16-bit tensors of a train step end behind C5), 'pyramid'
     (they run on through the laterals and the smoothing convolutions to p2..p5) or 'crops' (everything 'pyramid' does, and
-    the RPN, the make-up layer and RoIAlign read the 16-bit p2..p5 as well: crops16).  Every scope but 'trunk' needs a
-    16-bit TRAIN.ACT_PRECISION; ValueError otherwise, and for any other value."""
+    the RPN, the make-up layer and RoIAlign read the 16-bit p2..p5 as well: crops16) or 'heads' (everything 'crops' does,
+    and the box and mask heads run forward and backward on 16-bit channels-last crops: heads16).  Every scope but 'trunk'
+    needs a 16-bit TRAIN.ACT_PRECISION; ValueError otherwise, and for any other value."""
     train = getattr(config, "TRAIN", None)
     scope = getattr(train, "ACT_SCOPE", "trunk")
     prec = getattr(train, "ACT_PRECISION", "fp32")
     if not isinstance(scope, str) or scope not in SCOPES:
-        raise ValueError("TRAIN.ACT_SCOPE is 'trunk', 'pyramid' or 'crops', got %r (TRAIN.ACT_PRECISION = %r)" % (scope, prec))
+        raise ValueError("TRAIN.ACT_SCOPE is 'trunk', 'pyramid', 'crops' or 'heads', got %r (TRAIN.ACT_PRECISION = %r)" % (scope, prec))
     if scope != "trunk" and (not isinstance(prec, str) or prec not in _conv._LOWP):
         raise ValueError("TRAIN.ACT_SCOPE = %r needs TRAIN.ACT_PRECISION = 'bf16' or 'fp16', got %r" % (scope, prec))
     return scope

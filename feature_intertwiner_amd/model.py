@@ -13,6 +13,7 @@ from . import pyr16 as _pyr16
 from . import train16 as _train16
 from . import fpn16 as _fpn16
 from . import crops16 as _crops16
+from . import heads16 as _heads16
 import os as _os
 # the mask head's batch whose results nothing reads runs on the second stream (same-box A/B 120.3 -> 117.2 ms/step)
 _DEAD_SIDE = _os.environ.get('FI_DEAD_SIDE', '1') != '0'
@@ -41,6 +42,7 @@ class MaskRCNN(nn.Module):
         _train16.check_config(config)       # ValueError for a bad TRAIN.ACT_PRECISION; 16-bit + FPN_OT_LOSS is not built
         _fpn16.train_scope(config)          # ValueError for a TRAIN.ACT_SCOPE that its TRAIN.ACT_PRECISION cannot carry
         _crops16.check_config(config)       # NotImplementedError for what TRAIN.ACT_SCOPE = 'crops' cannot carry
+        _heads16.check_config(config)       # ... and for what 'heads' cannot: the same, and DEV.CLS_MERGE_FEAT
         self._build(config)
         self._initialize_weights()
         self.feature_buffer = None
@@ -150,6 +152,15 @@ class MaskRCNN(nn.Module):
         front = P_front if (split_mask and chain and _MASK_FRONT and 0 < P_front < cfg.ROIS.TRAIN_ROIS_PER_IMAGE) else None
         mask_box = None if ((split_mask and not front) or cfg.MRCNN.MASK_HEAD_ON_POSITIVE_SLOTS or not chain) \
             else _conv.GradBox()
+        # TRAIN.ACT_SCOPE 'heads' (16-bit p2..p5 under that scope): the Dev stage's crops are ONE node of heads16 whose
+        # readers share no tensor -- no front permutation of one big crop, no row gather, no mask box; the mask head's graph
+        # batch (the positive slots, or every slot) and its rest batch are crops of their own
+        heads16 = _act16.is_act16(p2) and _fpn16.train_scope(cfg) == "heads"
+        if heads16:
+            _heads16.require_gates()
+            front = mask_box = None
+            graph_slots = P_front if (cfg.MRCNN.MASK_HEAD_ON_POSITIVE_SLOTS or split_mask) else cfg.ROIS.TRAIN_ROIS_PER_IMAGE
+            heads_slots = (graph_slots, bool(split_mask))
         # The RPN losses read RPN.TRAIN_ANCHORS_PER_IMAGE sampled anchors per image: with conv.GATES the dense RPN runs
         # without a graph (the proposal layer needs every anchor) and the losses' graph is RPN.forward_rows on those rows
         rows = images.is_cuda and torch.is_grad_enabled() and _conv.GATES and self.rpn.anchor_stride == 1
@@ -207,7 +218,8 @@ class MaskRCNN(nn.Module):
         pooled_cls, pooled_mask, feat_out = self.dev_roi(mrcnn_maps, rois, target_class_ids, up_maps=up_maps,
                                                          level_info=(roi_lvl, counts_ready),
                                                          raw_grad_boxes=to_make_up if chain else None,
-                                                         mask_grad_box=mask_box, mask_front=front)
+                                                         mask_grad_box=mask_box, mask_front=front,
+                                                         heads_slots=heads_slots if heads16 else None)
         # the statistics the meta loss reads are complete here: workflow.compute_loss evaluates it on another stream from
         # this point on, next to the box and mask heads (its ~70 small kernels and the Sinkhorn launch are latency bound)
         self._stats_ready = None
@@ -225,7 +237,21 @@ class MaskRCNN(nn.Module):
 
         mrcnn_class_logits, _, mrcnn_bbox = self.classifier(pooled_cls, small_output_all, small_gt_all)
         mask_ids, mask_tgt = target_class_ids, target_mask
-        if cfg.MRCNN.MASK_HEAD_ON_POSITIVE_SLOTS or split_mask:
+        if heads16:
+            # (graph batch, rest batch or None), 16-bit channels-last: the rest batch -- computed, as the reference does,
+            # and read by nobody -- runs the inference form without a graph, on the second stream as the fp32 one does
+            pooled_mask, rest = pooled_mask
+            if rest is not None:
+                with torch.no_grad():
+                    if _DEAD_SIDE:
+                        dead = lambda t: (self.mask(t), None)[1]
+                        self._side_join = _lib.run_on_side_stream(dead, rest)
+                        rest.record_stream(_lib.side_stream(rest.device))
+                    else:
+                        self.mask(rest)
+            P = heads_slots[0]
+            mask_ids, mask_tgt = target_class_ids[:, :P], target_mask[:, :P]
+        elif cfg.MRCNN.MASK_HEAD_ON_POSITIVE_SLOTS or split_mask:
             # The reference runs the mask head on every RoI (lib/model.py:442) although only positive
             # RoIs enter the mask loss (lib/layers.py:905-934).  prepare_det_target puts the positives
             # of an image in its first slots, at most ROI_POSITIVE_RATIO * R of them, so the head's

@@ -22,6 +22,7 @@ from . import fpn16 as _fpn16
 from . import crops16 as _crops16
 from . import conv as _conv
 from . import head16 as _head16
+from . import heads16 as _heads16
 from . import pyr16 as _pyr16
 from . import roi16 as _roi16
 from .conv import (Conv2d, ConvTranspose2x2, ConvTranspose3x3, GradBox, conv1x1_class_rows, conv2d, conv_bias_relu,
@@ -279,8 +280,8 @@ class FPN(nn.Module):
         train16 = tact != "fp32" and mode == 'train' and x.is_cuda and torch.is_grad_enabled()
         # 'pyramid': the laterals and smoothing layers too (_pyramid_train16); 'crops': p2..p5 stay 16-bit behind them
         tscope = _fpn16.train_scope(self.config)
-        if train16 and tscope == "crops":
-            _crops16.require_gates()
+        if train16 and tscope in ("crops", "heads"):
+            _crops16.require_gates(tscope)
         x = conv_bn_act(x, self.C1[0], self.C1[1], relu=True)       # C1 = conv, bn, relu, pad, maxpool
         x = _pad_maxpool(x, self.C1[3], self.C1[4])
         if act:
@@ -310,8 +311,8 @@ class FPN(nn.Module):
         if act:
             c = {lvl: _act16.unpack(m) for lvl, m in c.items()}
             c2 = c[2]
-        if train16 and tscope in ("pyramid", "crops"):
-            return self._pyramid_train16(c, boxes, keep16=tscope == "crops") + [ot_loss]
+        if train16 and tscope in ("pyramid", "crops", "heads"):
+            return self._pyramid_train16(c, boxes, keep16=tscope != "pyramid") + [ot_loss]
         if train16:
             # the laterals read fp32 NCHW maps; their data gradients come back through the unpack's backward, which packs
             # them and leaves them in the next stage's lateral_box (when its first block took it) instead of the
@@ -588,6 +589,7 @@ class Dev(nn.Module):
         if _pyr16.act_scope(config.MODEL) in ('roi', 'detect'):
             self._require_roi16()
         _crops16.check_config(config)       # TRAIN.ACT_SCOPE = 'crops': what the 16-bit route to the crops cannot carry
+        _heads16.check_config(config)       # ... 'heads': the same, and DEV.CLS_MERGE_FEAT
         if self.use_dev:
             self.feat_pool_size = config.DEV.FEAT_BRANCH_POOL_SIZE
             assert self.feat_pool_size % 2 == 0, 'pool size of feature branch has to be even'
@@ -769,11 +771,15 @@ class Dev(nn.Module):
         return t
 
     def forward(self, x, rois, roi_cls_gt=None, up_maps=None, level_info=None, raw_grad_boxes=None, mask_grad_box=None,
-                mask_front=None):
+                mask_front=None, heads_slots=None):
         """raw_grad_boxes: per level, the GradBox make_up_maps(take_from=...) takes from -- the big-box crop of the RAW
         level maps leaves its map gradients there.  mask_grad_box: the mask head (the second reader of the 14 x 14
         crops, applied after this stage) leaves its input gradient there; the row gather in front of the feature
-        extractor adds its own rows into it (conv.take_rows)."""
+        extractor adds its own rows into it (conv.take_rows).
+        heads_slots = (P, want_rest) (TRAIN.ACT_SCOPE 'heads', 16-bit make-up maps with a graph): the crops are ONE node of
+        heads16 -- the 7 x 7 crops of every RoI and the 14 x 14 crops of the slots s < P of every image as 16-bit
+        channels-last tensors, those of the other slots without a graph when want_rest, and the feature extractor's rows as
+        fp32 crops of their own; the second return value is then the pair (graph batch, rest batch or None)."""
         cfg = self.config
         bs, R = rois.size(0), rois.size(1)
         boxes = rois.reshape(-1, 4)
@@ -799,14 +805,35 @@ class Dev(nn.Module):
         if not static:
             n2, n3, n4, n5 = (int(v) for v in counts_ready().tolist())
         group = CropGradGroup()      # both crops' gradients accumulate in ONE set of buffers (no add pass per level)
+        feat_rows = pre_index = None   # TRAIN.ACT_SCOPE 'heads': the feature extractor's own crop, the static index made early
         if _act16.is_act16(up_maps[0]) and torch.is_grad_enabled() and up_maps[0].requires_grad:
             # TRAIN.ACT_SCOPE 'crops': both crops are ONE autograd node (crops16.pyramid_crops16) that returns 16-bit map
             # gradients, masked for the make-up layer
             self._require_roi16()
-            perm, inv = self._front_permutation(bs, R, front, rois.device) if front else (None, None)
-            mask_spec = (boxes[perm], box_ind[perm], level[perm]) if front else (boxes, box_ind, level)
-            pooled, mask_and_feat = _crops16.pyramid_crops16(up_maps, [(boxes, box_ind, level, self.pool_size),
-                                                                       mask_spec + (self.mask_pool_size,)])
+            if heads_slots is not None:
+                # the feature extractor's rows are a crop of their own: its row order is needed before the node is made
+                P, want_rest = heads_slots
+                if static:
+                    gt_i = roi_cls_gt.reshape(-1).to(torch.int32) if train_phase else None
+                    pre_index = self._static_index(level, gt_i, self.num_classs, (3 * bs * R + 63) // 64 * 64)
+                    order = pre_index[0]
+                else:
+                    order = torch.sort(level, stable=True)[1][:min((n2 + n3 + n4 + 63) // 64 * 64, bs * R)]
+                mps = self.mask_pool_size
+                spec = lambda i: (boxes[i], box_ind[i], level[i], mps)
+                if 0 < P < R:
+                    perm, _ = self._front_permutation(bs, R, P, rois.device)
+                    graph, rest = spec(perm[:bs * P]), (spec(perm[bs * P:]) if want_rest else None)
+                else:
+                    graph, rest = (boxes, box_ind, level, mps), None
+                pooled, m_graph, m_rest, feat_rows = _heads16.pyramid_crops_heads16(
+                    up_maps, (boxes, box_ind, level, self.pool_size), graph, rest, spec(order))
+                mask_and_feat, inv = (m_graph, m_rest), None
+            else:
+                perm, inv = self._front_permutation(bs, R, front, rois.device) if front else (None, None)
+                mask_spec = (boxes[perm], box_ind[perm], level[perm]) if front else (boxes, box_ind, level)
+                pooled, mask_and_feat = _crops16.pyramid_crops16(up_maps, [(boxes, box_ind, level, self.pool_size),
+                                                                           mask_spec + (self.mask_pool_size,)])
         else:
             pooled = self._crop(up_maps, boxes, box_ind, level, self.pool_size, group)
             if front:
@@ -824,7 +851,7 @@ class Dev(nn.Module):
         total_box = bs * R
         if static:
             return self._forward_static(x, boxes, box_ind, level, counts_ready, roi_cls_gt, pooled, mask_and_feat, inv,
-                                        mask_grad_box, total_box)
+                                        mask_grad_box, total_box, pre_index, feat_rows)
         n_small = n2 + n3 + n4
         # The feature extractor's fully connected stages are matrix products over the rows fed to it; their kernels
         # take row counts that are multiples of 64, so up to 63 further RoIs (the first level-5 ones in the sorted
@@ -832,7 +859,8 @@ class Dev(nn.Module):
         # or masked by level.
         n_rows = min((n_small + 63) // 64 * 64, total_box)
         order = torch.sort(level, stable=True)[1][:n_rows]
-        small_output = self._feat_extract(take_rows(mask_and_feat, order if inv is None else inv[order], mask_grad_box))
+        small_output = self._feat_extract(feat_rows if feat_rows is not None else
+                                          take_rows(mask_and_feat, order if inv is None else inv[order], mask_grad_box))
         if cfg.DEV.LOSS_CHOICE != 'ot':
             small_output = self.last_op(small_output)
         small_output = small_output.view(n_rows, -1)
@@ -991,7 +1019,7 @@ class Dev(nn.Module):
         return order, small_cls, small_gt, small_on, big_idx, big_level, big_cls, counts[4:5]
 
     def _forward_static(self, x, boxes, box_ind, level, per_level, roi_cls_gt, pooled, mask_and_feat, inv, mask_grad_box,
-                        total_box):
+                        total_box, pre_index=None, feat_rows=None):
         """The part of forward() behind the two crops with shapes that do not depend on the RoIs (see static_shapes).
         One launch (fi_dev_stage_index) makes every index the stage needs; the class means of the three levels are ONE
         launch over 3 K classes (class = (level - 2) K + gt: the same rows in the same order per class as three launches)."""
@@ -1001,8 +1029,12 @@ class Dev(nn.Module):
         train_phase = roi_cls_gt is not None
         gt = roi_cls_gt.reshape(-1).to(torch.int32) if train_phase else None
         cap = (3 * total_box + 63) // 64 * 64            # whole row tiles of the fully connected stages: no padding copy
-        order, small_cls, small_gt_all, small_on, big_idx, big_level, big_cls, live = self._static_index(level, gt, K, cap)
-        small_output = self._feat_extract(take_rows(mask_and_feat, order if inv is None else inv[order], mask_grad_box))
+        # (pre_index / feat_rows, TRAIN.ACT_SCOPE 'heads': the index was made before the crops, whose node returns the
+        # feature extractor's rows as a crop of their own)
+        order, small_cls, small_gt_all, small_on, big_idx, big_level, big_cls, live = \
+            pre_index if pre_index is not None else self._static_index(level, gt, K, cap)
+        small_output = self._feat_extract(feat_rows if feat_rows is not None else
+                                          take_rows(mask_and_feat, order if inv is None else inv[order], mask_grad_box))
         if cfg.DEV.LOSS_CHOICE != 'ot':
             small_output = self.last_op(small_output)
         small_output = small_output.view(total_box, -1)
@@ -1058,6 +1090,8 @@ class Classifier(nn.Module):
 
     def forward(self, x, small_feat_input=None, small_gt_index=None, mode='train'):
         if _act16.is_act16(x):
+            if torch.is_grad_enabled() and x.requires_grad:
+                return self._forward_train16(x, small_feat_input)       # a graph on 16-bit crops: the training branch
             return self._forward16(x, small_feat_input)
         x = conv_bn_act(x, self.conv1, self.bn1, relu=True)
         cfg = self.config
@@ -1086,6 +1120,20 @@ class Classifier(nn.Module):
         bbox = bbox.view(bbox.size(0), -1, 4)
         return [logits, probs, bbox]
 
+
+    def _forward_train16(self, x, small_feat_input=None):
+        """16-bit channels-last crops [n, depth, 7, 7] that require grad: _forward16's three launches with a graph.  The
+        full-window layer and conv2 run on 16-bit tensors forward and backward; each layer is the only reader of the one in
+        front, so conv2 and the stacked output layer run the gated data gradient and neither conv1 nor conv2 a relu_grad16.
+        Only the logits and the boxes are fp32."""
+        if small_feat_input is not None and self.config.DEV.SWITCH and self.config.DEV.CLS_MERGE_FEAT:
+            raise NotImplementedError("DEV.CLS_MERGE_FEAT on 16-bit crops is not built")
+        x = _heads16.window_bn_act16(x, self.conv1, self.bn1)
+        x = _train16.conv_bn_act16(x, self.conv2, self.bn2, relu=True, gate_dx=True)
+        heads = _heads16.stacked_out16(x, (self.linear_class, self.linear_bbox), gate_dx=True)
+        nc = self.linear_class.weight.shape[0]
+        logits, bbox = heads[:, :nc].contiguous(), heads[:, nc:].contiguous()
+        return [logits, self.softmax(logits), bbox.view(bbox.size(0), -1, 4)]
 
     def _forward16(self, x, small_feat_input=None):
         """16-bit channels-last crops [n, depth, 7, 7] (MODEL.ACT_SCOPE 'detect', inference): the full-window layer on the
@@ -1127,8 +1175,11 @@ class Mask(nn.Module):
         select_class[n] for RoI n, [N, 2, 2, 14, 14] -- conv5 still evaluates every class (the reference's schedule), but
         its backward then knows that the gradient has one non-zero channel per RoI (conv.conv1x1_class_rows)."""
         if _act16.is_act16(x):
+            if torch.is_grad_enabled() and select_class is not None and not shuffled and not activate:
+                return self._forward_train16(x, select_class)          # a graph on 16-bit crops: the training branch
             if not (shuffled and activate) or select_class is not None:
-                raise _lib.FiError("Mask on 16-bit crops is the inference form: shuffled, activated, every class")
+                raise _lib.FiError("Mask on 16-bit crops is the inference form (shuffled, activated, every class) or, with "
+                                   "grad mode on, the training form (unshuffled logits of select_class)")
             return self._forward16(x)
         # input_grad_box: x has another reader whose backward runs later and takes the gradient from there (Dev.forward)
         give = input_grad_box if (input_grad_box is not None and input_grad_box.taker and _fused_path(x, self.bn1)) else None
@@ -1164,6 +1215,20 @@ class Mask(nn.Module):
         if not shuffled:
             return y
         return y.permute(0, 3, 4, 1, 5, 2).reshape(n, y.shape[3], 2 * h, 2 * w)
+
+    def _forward_train16(self, x, select_class):
+        """16-bit channels-last crops [n, depth, 14, 14] with grad mode on: the logits of class select_class[i] of RoI i,
+        [n, 2, 2, 14, 14] fp32, every layer forward and backward on 16-bit channels-last tensors.  The forwards are
+        _forward16's launches up to u; conv5 evaluates every class in one fp32 output launch and the class column is
+        gathered behind it.  Each layer is the only reader of the one in front: conv2..conv4, the transposed convolution
+        and conv5's class-row backward leave the masked gradient and its column sums in their input's Gate16, and no
+        layer of the head runs a relu_grad16.  conv1's data gradient goes to autograd (the crop node in front of it)."""
+        x = _train16.conv_bn_act16(x, self.conv1, self.bn1, relu=True)
+        x = _train16.conv_bn_act16(x, self.conv2, self.bn2, relu=True, gate_dx=True)
+        x = _train16.conv_bn_act16(x, self.conv3, self.bn3, relu=True, gate_dx=True)
+        x = _train16.conv_bn_act16(x, self.conv4, self.bn4, relu=True, gate_dx=True)
+        u = _heads16.deconv2x2_bias_act16(x, self.deconv, gate_dx=True)
+        return _heads16.class_rows_out16(u, self.conv5, select_class.reshape(-1).to(torch.int64))
 
     def _forward16(self, x):
         """16-bit channels-last crops [n, depth, 14, 14] (MODEL.ACT_SCOPE 'detect', inference): four 3x3 layers and the
