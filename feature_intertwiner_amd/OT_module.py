@@ -19,7 +19,6 @@ on the critic's ReLU output, :111-112, raises in modern autograd; forward values
 identical).
 """
 import ctypes
-import os
 
 import torch
 import torch.nn as nn
@@ -30,32 +29,18 @@ from .conv import Conv1d, Conv2d, ConvTranspose3x3
 
 EPS = 1e-20
 
-OT_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfi_ot.so")
+OT_LIB_PATH = _lib.sublibrary_path("ot")
 _p, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 # name -> (restype, argtypes); mirrors include/fi_ot.h one to one
 OT_SIGNATURES = {
     "fi_ot_sinkhorn_backprop_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "fi_ot_sinkhorn_backprop": (_i, [_p, _p, _i, _i, _i, _f, _i, _i, _p, _p, _p, ctypes.c_size_t, _p]),
 }
-_ot = None
 
 
 def load_ot():
     """Load libfi_ot.so (after libfi_hip.so, which it links against) and attach the signatures."""
-    global _ot
-    if _ot is not None:
-        return _ot
-    _lib.load()
-    if not os.path.exists(OT_LIB_PATH):
-        raise _lib.FiError("libfi_ot.so not found at %s -- build it with `python -m feature_intertwiner_amd.build` "
-                           "(there is no CPU/PyTorch fallback)" % OT_LIB_PATH)
-    L = ctypes.CDLL(OT_LIB_PATH)
-    for name, (res, args) in OT_SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
-    _ot = L
-    return L
+    return _lib.load_sublibrary("ot", OT_SIGNATURES)
 
 
 def _cost_backward(cost_mode, x, y, plan, grad_loss, difference_form=False):

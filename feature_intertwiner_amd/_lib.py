@@ -280,6 +280,38 @@ def load():
     return L
 
 
+_SUBLIBS = {}
+
+
+def sublibrary_path(stem):
+    return os.path.join(_HERE, "libfi_%s.so" % stem)
+
+
+def load_sublibrary(stem, signatures):
+    """Load libfi_<stem>.so (after libfi_hip.so, which it links against) and attach `signatures`, name -> (restype,
+    argtypes); once per stem.  Raises FiError if the file is absent."""
+    L = _SUBLIBS.get(stem)
+    if L is None:
+        load()
+        path = sublibrary_path(stem)
+        if not os.path.exists(path):
+            raise FiError("libfi_%s.so not found at %s -- build it with `python -m feature_intertwiner_amd.build` "
+                          "(there is no CPU/PyTorch fallback)" % (stem, path))
+        L = ctypes.CDLL(path)
+        for name, (res, args) in signatures.items():
+            fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
+            fn.restype = res
+            fn.argtypes = args
+        _SUBLIBS[stem] = L
+    return L
+
+
+def zero_counters(counters):
+    """reset_stats() of the modules that keep host counters in a dict."""
+    for k in counters:
+        counters[k] = 0
+
+
 def check(rc, what):
     if rc != 0:
         msg = load().fi_last_error().decode("utf-8", "replace")

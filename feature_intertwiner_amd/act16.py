@@ -7,14 +7,13 @@ sees logical NCHW, the memory is NHWC.  Which layers the kernel takes is decided
 here restates its rules, and a layer it refuses is an error -- there is no fallback to another path.
 """
 import ctypes
-import os
 
 import torch
 
 from . import _lib
 from . import conv as _conv
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfi_act16.so")
+LIB_PATH = _lib.sublibrary_path("act16")
 _cp, _ci = ctypes.c_void_p, ctypes.c_int
 _FWD = (_ci, [_cp, _cp, _cp, _cp, _cp, _cp, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _cp])
 _CAST = (_ci, [_cp, _cp, _ci, _ci, _ci, _ci, _cp])
@@ -28,27 +27,13 @@ SIGNATURES = {
     "fi_act16_unpack_bf16": _CAST,
     "fi_act16_unpack_f16": _CAST,
 }
-_act16 = None
 _PRECISION_OF = {dtype: prec for prec, (_, dtype) in _conv._LOWP.items()}      # torch dtype -> 'bf16' / 'fp16'
 _STATS = {"conv": 0, "pack": 0, "unpack": 0}
 
 
 def load():
     """Load libfi_act16.so (after libfi_hip.so, which it links against) and attach the signatures."""
-    global _act16
-    if _act16 is not None:
-        return _act16
-    _lib.load()
-    if not os.path.exists(LIB_PATH):
-        raise _lib.FiError("libfi_act16.so not found at %s -- build it with `python -m feature_intertwiner_amd.build` "
-                           "(there is no CPU/PyTorch fallback)" % LIB_PATH)
-    L = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
-    _act16 = L
-    return L
+    return _lib.load_sublibrary("act16", SIGNATURES)
 
 
 def stats():
@@ -57,8 +42,7 @@ def stats():
 
 
 def reset_stats():
-    for k in _STATS:
-        _STATS[k] = 0
+    _lib.zero_counters(_STATS)
 
 
 def dtype_of(precision):
@@ -125,14 +109,25 @@ def conv_bn_act16(x16, conv, bn, relu=True, residual=None):
     if torch.is_grad_enabled():
         raise _lib.FiError("conv_bn_act16 is forward only: call it under torch.no_grad() (training on 16-bit activation "
                            "tensors is not built)")
+    scale, shift = eval_fold("conv_bn_act16", conv, bn)
+    return _conv16("conv_bn_act16", x16, prec, conv, scale, shift, relu, residual)
+
+
+def require_eval_bn(what, bn):
     if bn.training or not bn.track_running_stats:
-        raise _lib.FiError("conv_bn_act16 folds an eval-mode BatchNorm with running statistics; got one in training mode")
+        raise _lib.FiError("%s folds an eval-mode BatchNorm with running statistics; got one in training mode" % what)
+
+
+def eval_fold(what, conv, bn):
+    """(scale, shift) of the eval-mode `bn` behind `conv`: the cached fold of conv.refresh_bn_folds, refreshed when a
+    parameter changed.  Raises _lib.FiError for one in training mode."""
+    require_eval_bn(what, bn)
     _conv._FOLD_PAIRS[bn] = conv
     fold = _conv._cached_fold(conv, bn)
     if fold is None:
         _conv.refresh_bn_folds()
         fold = _conv._cached_fold(conv, bn)
-    return _conv16("conv_bn_act16", x16, prec, conv, fold[0], fold[1], relu, residual)
+    return fold
 
 
 def weight16(weight, dtype):

@@ -7,7 +7,6 @@ csrc/cocoeval.hip (include/fi_cocoeval.h); this module packs the dicts into devi
 `torch.sort` on device tensors) and reads the result tables back.  Every number is bit-equal to the reference's
 (tests/golden/cocoeval.npz).  Decisions where the reference raises or misbehaves are in DESIGN.md §2."""
 import ctypes
-import os
 
 import numpy as np
 import torch
@@ -15,7 +14,7 @@ import torch
 from . import _lib
 from ._lib import FiError, check, current_stream
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfi_cocoeval.so")
+LIB_PATH = _lib.sublibrary_path("cocoeval")
 _p, _i, _ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
 # name -> (restype, argtypes); mirrors include/fi_cocoeval.h one to one
 SIGNATURES = {
@@ -25,25 +24,11 @@ SIGNATURES = {
     "fi_coco_match": (_i, [_ll] + [_p] * 11 + [_i, _i] + [_p] * 5 + [_p]),
     "fi_coco_accumulate": (_i, [_i] + [_p] * 10 + [_i] * 4 + [_p] * 3 + [_p]),
 }
-_coco = None
 
 
 def load():
     """Load libfi_cocoeval.so (after libfi_hip.so, which it links against) and attach the signatures."""
-    global _coco
-    if _coco is not None:
-        return _coco
-    _lib.load()
-    if not os.path.exists(LIB_PATH):
-        raise FiError("libfi_cocoeval.so not found at %s -- build it with `python -m feature_intertwiner_amd.build` "
-                      "(there is no CPU/PyTorch fallback)" % LIB_PATH)
-    L = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
-    _coco = L
-    return L
+    return _lib.load_sublibrary("cocoeval", SIGNATURES)
 
 
 class Params:

@@ -6,7 +6,6 @@ csrc/cocomask.hip (include/fi_cocomask.h).  This module flattens the Python list
 library's bound and assembles one (rles, counts) pair in the layout of cocoeval.py.  Every count is bit-equal to the
 reference's (tests/golden/cocopoly.npz).  Decisions where the reference raises or misbehaves are in DESIGN.md §2."""
 import ctypes
-import os
 
 import numpy as np
 import torch
@@ -14,7 +13,7 @@ import torch
 from . import _lib
 from ._lib import FiError, check, current_stream
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfi_cocomask.so")
+LIB_PATH = _lib.sublibrary_path("cocomask")
 _p, _i, _ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
 # name -> (restype, argtypes); mirrors include/fi_cocomask.h one to one
 SIGNATURES = {
@@ -23,25 +22,11 @@ SIGNATURES = {
     "fi_cocomask_from_polygons": (_i, [_p, _p, _p, _p, _ll, _ll, _p, _p, _p, _p]),
     "fi_cocomask_merge": (_i, [_p, _p, _p, _p, _ll, _ll, _i, _p, _p, _p, _p]),
 }
-_mask = None
 
 
 def load():
     """Load libfi_cocomask.so (after libfi_hip.so, which it links against) and attach the signatures."""
-    global _mask
-    if _mask is not None:
-        return _mask
-    _lib.load()
-    if not os.path.exists(LIB_PATH):
-        raise FiError("libfi_cocomask.so not found at %s -- build it with `python -m feature_intertwiner_amd.build` "
-                      "(there is no CPU/PyTorch fallback)" % LIB_PATH)
-    L = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
-    _mask = L
-    return L
+    return _lib.load_sublibrary("cocomask", SIGNATURES)
 
 
 def _host_ptr(a):

@@ -1688,33 +1688,19 @@ class Conv1d(nn.Conv1d):
 # Backward, existing entry points only: dx is that convolution's forward of dy, dw its weight gradient with dy in the
 # input role and x in the output-gradient role (already in the parameter's layout), the ReLU mask, BatchNorm scale and
 # per-channel sums one fi_bn_act_backward pass.  Always fp32, whatever MODEL.CONV_PRECISION says.
-CONVT_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfi_convt.so")
+CONVT_LIB_PATH = _lib.sublibrary_path("convt")
 _cp, _ci = ctypes.c_void_p, ctypes.c_int
 # name -> (restype, argtypes); mirrors include/fi_convt.h one to one
 CONVT_SIGNATURES = {
     "fi_conv_transpose3x3s2_eligible": (_ci, [_ci, _ci, _ci, _ci, _ci, _ci, _cp, _cp]),
     "fi_conv_transpose3x3s2_forward": (_ci, [_cp, _cp, _cp, _cp, _cp, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _cp]),
 }
-_convt = None
 CONVT_COMPOSE_ONLY = False        # True: eligible shapes take the four-class composition too (tests, scripts/convt_probe.py)
 
 
 def load_convt():
     """Load libfi_convt.so (after libfi_hip.so, which it links against) and attach the signatures."""
-    global _convt
-    if _convt is not None:
-        return _convt
-    _lib.load()
-    if not os.path.exists(CONVT_LIB_PATH):
-        raise _lib.FiError("libfi_convt.so not found at %s -- build it with `python -m feature_intertwiner_amd.build` "
-                           "(there is no CPU/PyTorch fallback)" % CONVT_LIB_PATH)
-    L = ctypes.CDLL(CONVT_LIB_PATH)
-    for name, (res, args) in CONVT_SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
-    _convt = L
-    return L
+    return _lib.load_sublibrary("convt", CONVT_SIGNATURES)
 
 
 def _convt_compose(x, w, bias, scale, relu):

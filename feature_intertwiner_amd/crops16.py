@@ -13,7 +13,6 @@ Plain allocations, single process, as train16 and fpn16.  Which calls the kernel
 alone; a call it refuses is an error -- there is no fallback to another path.
 """
 import ctypes
-import os
 
 import torch
 
@@ -24,7 +23,7 @@ from . import fpn16
 from . import roi16
 from . import train16
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfi_crops16.so")
+LIB_PATH = _lib.sublibrary_path("crops16")
 _cp, _ci = ctypes.c_void_p, ctypes.c_int
 _PATCH_FWD = (_ci, [_cp, _cp, _cp, _cp, _ci, _ci, _cp, _cp, _ci, _ci, _ci, _cp, _cp])
 _PATCH_BWD = (_ci, [_cp, _cp, _cp, _cp, _cp, _ci, _ci, _cp, _cp, _ci, _ci, _ci, _cp])
@@ -41,26 +40,12 @@ SIGNATURES = {
 }
 PATCH_FWD, PATCH_BWD, GATE_PACK = 0, 1, 2          # FI_CROPS16_* kinds of fi_crops16_eligible
 SCOPE = "crops"
-_crops16 = None
 _STATS = {"patch_fwd": 0, "patch_bwd": 0, "gate_pack": 0, "crops": 0}
 
 
 def load():
     """Load libfi_crops16.so (after libfi_hip.so, which it links against) and attach the signatures."""
-    global _crops16
-    if _crops16 is not None:
-        return _crops16
-    _lib.load()
-    if not os.path.exists(LIB_PATH):
-        raise _lib.FiError("libfi_crops16.so not found at %s -- build it with `python -m feature_intertwiner_amd.build` "
-                           "(there is no CPU/PyTorch fallback)" % LIB_PATH)
-    L = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
-    _crops16 = L
-    return L
+    return _lib.load_sublibrary("crops16", SIGNATURES)
 
 
 def stats():
@@ -70,8 +55,7 @@ def stats():
 
 
 def reset_stats():
-    for k in _STATS:
-        _STATS[k] = 0
+    _lib.zero_counters(_STATS)
 
 
 def check_config(config):

@@ -13,7 +13,6 @@ Plain allocations, single process, as train16.  Which calls the kernel takes is 
 it refuses is an error -- there is no fallback to another path.
 """
 import ctypes
-import os
 
 import torch
 
@@ -25,7 +24,7 @@ from . import pyr16
 from . import step_state
 from . import train16
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfi_fpn16.so")
+LIB_PATH = _lib.sublibrary_path("fpn16")
 _cp, _ci = ctypes.c_void_p, ctypes.c_int
 _TOPDOWN = (_ci, [_cp, _cp, _cp, _cp, _ci, _ci, _ci, _ci, _cp])
 # name -> (restype, argtypes); mirrors include/fi_fpn16.h one to one
@@ -36,26 +35,12 @@ SIGNATURES = {
 }
 SCOPES = ("trunk", "pyramid", "crops", "heads")
 _BIAS_ONLY = "bias-only"          # where grad16.weight_t16 keeps the key of a BatchNorm fold (a tuple): no fold, scale 1
-_fpn16 = None
 _STATS = {"topdown": 0, "sums": 0, "lateral": 0, "conv": 0, "top_to_autograd": 0, "weights": 0}
 
 
 def load():
     """Load libfi_fpn16.so (after libfi_hip.so, which it links against) and attach the signatures."""
-    global _fpn16
-    if _fpn16 is not None:
-        return _fpn16
-    _lib.load()
-    if not os.path.exists(LIB_PATH):
-        raise _lib.FiError("libfi_fpn16.so not found at %s -- build it with `python -m feature_intertwiner_amd.build` "
-                           "(there is no CPU/PyTorch fallback)" % LIB_PATH)
-    L = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
-    _fpn16 = L
-    return L
+    return _lib.load_sublibrary("fpn16", SIGNATURES)
 
 
 def stats():
@@ -67,8 +52,7 @@ def stats():
 
 
 def reset_stats():
-    for k in _STATS:
-        _STATS[k] = 0
+    _lib.zero_counters(_STATS)
 
 
 def train_scope(config):
@@ -156,13 +140,6 @@ def _will_take(box):
         box.taker = True
 
 
-def _dw_view(dwp, R, S):
-    """The tap-major weight gradient with the strides of its parameter, as train16 gives them: [Cout, Cin, 1, 1] contiguous
-    for a 1x1 layer, channels-last strides for a 3x3 one (what prepare_step gives the weight)."""
-    Cout, _, _, Cin = dwp.shape
-    return dwp.view(Cout, Cin, 1, 1) if R * S == 1 else dwp.permute(0, 3, 1, 2)
-
-
 class _Lateral16Fn(torch.autograd.Function):
     """y = round16((conv1x1(x16) + bias) + top16 at half resolution): fi_pyr16_lateral.  Backward, with dy the gradient
     autograd delivers and `fine` what the next finer lateral left in `top_grad_from`: g = round16(dy + 2x2 sums of fine)
@@ -184,7 +161,7 @@ class _Lateral16Fn(torch.autograd.Function):
         need_x, need_w, need_b, need_top = ctx.needs_input_grad[:4]
         dy = dy.contiguous(memory_format=torch.channels_last)
         g, s = _own_plus_fine(dy, _take(ctx.top_grad_from), need_b)
-        dw = _dw_view(grad16.wgrad16(g, x16, 1, 1, 1, 0), 1, 1) if need_w else None
+        dw = train16.dw_view16(grad16.wgrad16(g, x16, 1, 1, 1, 0), 1, 1) if need_w else None
         dx = None
         if need_x:
             dx = grad16.dgrad16(g, weight_t16(ctx.conv, x16.dtype), (x16.shape[2], x16.shape[3]), 1, 0)
@@ -232,11 +209,8 @@ def lateral16(x16, conv, top16, top_grad_to=None, top_grad_from=None, dx_give_to
     _require_bias_layer("fpn16.lateral16", conv)
     N, Cin, H, W = x16.shape
     Cout = conv.weight.shape[0]
+    train16.require_backward16("fpn16.lateral16", (N, H, W, Cin, Cout, 1, 1, 1, 0), relu=False)
     if N > 0:
-        geom = (N, H, W, Cin, Cout, 1, 1, 1, 0)
-        L = grad16.load()
-        for kind, name in ((grad16.WGRAD, "wgrad"), (grad16.DGRAD, "dgrad")):
-            grad16._require_eligible(L, "fpn16.lateral16 (%s)" % name, kind, geom, None, None, None, None)
         if load().fi_fpn16_eligible(N, H, W, Cout, None, None, None, None) != 1:
             raise _lib.FiError("fpn16.lateral16: fi_fpn16_eligible refuses this layer (N %d, H %d, W %d, C %d); there is no "
                                "fallback" % (N, H, W, Cout))
@@ -274,16 +248,10 @@ class _ConvBiasAct16Fn(torch.autograd.Function):
             g, s = grad16.relu_grad16(dy, y, relu=True, colsum=need_b)
         else:
             g, s = _own_plus_fine(dy, fine, need_b)
-        dw = _dw_view(grad16.wgrad16(g, x16, R, S, stride, pad), R, S) if need_w else None
+        dw = train16.dw_view16(grad16.wgrad16(g, x16, R, S, stride, pad), R, S) if need_w else None
         dx = None
         if need_x:
-            wt = weight_t16(conv, x16.dtype)
-            hw = (x16.shape[2], x16.shape[3])
-            if ctx.in_gate is not None:
-                dx, s_in = train16.dgrad_gated16(g, wt, x16, hw, stride, pad, colsum=True)
-                ctx.in_gate.leave(dx, s_in)
-            else:
-                dx = grad16.dgrad16(g, wt, hw, stride, pad)
+            dx = train16.data_grad16(g, weight_t16(conv, x16.dtype), x16, ctx.in_gate, stride, pad)
         return dx, dw, s, None, None, None, None
 
 
@@ -300,16 +268,9 @@ def conv_bias_act16(x16, conv, relu=False, gate_dx=False, top_grad_from=None):
     N, Cin, H, W = x16.shape
     Cout, _, R, S = conv.weight.shape
     in_gate = train16._claim_gate16(x16, gate_dx)
+    stride, pad = conv.stride[0], conv.padding[0]
+    train16.require_backward16("fpn16.conv_bias_act16", (N, H, W, Cin, Cout, R, S, stride, pad), relu, in_gate)
     if N > 0:
-        stride, pad = conv.stride[0], conv.padding[0]
-        geom = (N, H, W, Cin, Cout, R, S, stride, pad)
-        L = grad16.load()
-        for kind, name in ((grad16.WGRAD, "wgrad"), (grad16.DGRAD, "dgrad")) + \
-                (((grad16.RELU_GRAD, "relu_grad"),) if relu else ()):
-            grad16._require_eligible(L, "fpn16.conv_bias_act16 (%s)" % name, kind, geom, None, None, None, None)
-        if in_gate is not None and train16.load().fi_train16_eligible(*geom, None, None, None, None) != 1:
-            raise _lib.FiError("fpn16.conv_bias_act16: fi_train16_eligible refuses this layer %s; there is no fallback"
-                               % (geom,))
         OH, OW = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - S) // stride + 1
         if OH < 1 or OW < 1 or load().fi_fpn16_eligible(N, OH, OW, Cout, None, None, None, None) != 1:
             raise _lib.FiError("fpn16.conv_bias_act16: fi_fpn16_eligible refuses this layer's output (N %d, H %d, W %d, "

@@ -8,7 +8,6 @@ layer, which calls the operators here.  Which layers the kernels take is decided
 fi_grad16_eligible alone; nothing here restates its rules, and a layer it refuses is an error -- there is no fallback.
 """
 import ctypes
-import os
 
 import torch
 
@@ -17,7 +16,7 @@ from . import act16
 from . import conv as _conv
 from . import step_state
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfi_grad16.so")
+LIB_PATH = _lib.sublibrary_path("grad16")
 _cp, _ci = ctypes.c_void_p, ctypes.c_int
 _RELU = (_ci, [_cp, _cp, _cp, _cp, _ci, _ci, _ci, _ci, _ci, _cp])
 _DGRAD = (_ci, [_cp, _cp, _cp, _cp, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _cp])
@@ -33,26 +32,12 @@ SIGNATURES = {
     "fi_grad16_conv_wgrad_f16": _WGRAD,
 }
 RELU_GRAD, DGRAD, WGRAD = 0, 1, 2          # FI_GRAD16_* kinds of fi_grad16_eligible
-_grad16 = None
 _STATS = {"relu_grad": 0, "dgrad": 0, "wgrad": 0, "weights": 0}
 
 
 def load():
     """Load libfi_grad16.so (after libfi_hip.so, which it links against) and attach the signatures."""
-    global _grad16
-    if _grad16 is not None:
-        return _grad16
-    _lib.load()
-    if not os.path.exists(LIB_PATH):
-        raise _lib.FiError("libfi_grad16.so not found at %s -- build it with `python -m feature_intertwiner_amd.build` "
-                           "(there is no CPU/PyTorch fallback)" % LIB_PATH)
-    L = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
-    _grad16 = L
-    return L
+    return _lib.load_sublibrary("grad16", SIGNATURES)
 
 
 def stats():
@@ -62,8 +47,7 @@ def stats():
 
 
 def reset_stats():
-    for k in _STATS:
-        _STATS[k] = 0
+    _lib.zero_counters(_STATS)
 
 
 def _require_eligible(L, what, kind, geom, *ptrs):
@@ -165,70 +149,16 @@ def weight_t16(conv, bn, scale, dtype):
     return wt
 
 
-class _ConvBnAct16Fn(torch.autograd.Function):
-    """y = act(conv(x16, W) * scale + shift (+ residual)), scale / shift the eval-BatchNorm fold.  Backward, with
-    g = dy * (y > 0): s = sum_p g (relu_grad), dW' = the weight gradient of the UNSCALED g (wgrad), then
-    fi_bn_fold_grad: dW = scale * dW' in place, d gamma = inv_std (<W, dW'> + (conv_bias - mean) s), d conv_bias =
-    scale * s; d beta = s; dx = the data gradient of g on the SCALED weight (dgrad); d residual = g."""
-
-    @staticmethod
-    def forward(ctx, x16, weight, bias, gamma, beta, residual, conv, bn, relu, prec, scale, shift):
-        y = act16._conv16("grad16.conv_bn_act16", x16, prec, conv, scale, shift, relu, residual)
-        ctx.save_for_backward(x16, y, weight, scale)
-        ctx.conv, ctx.bn, ctx.relu, ctx.has_res = conv, bn, relu, residual is not None
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x16, y, w, scale = ctx.saved_tensors
-        conv, bn = ctx.conv, ctx.bn
-        need_x, need_w, need_b, need_gamma, need_beta, need_res = ctx.needs_input_grad[:6]
-        Cout, Cin, R, S = w.shape
-        stride, pad = conv.stride[0], conv.padding[0]
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        want_sums = need_w or need_b or need_gamma or need_beta
-        g, s = relu_grad16(dy, y, relu=ctx.relu, colsum=want_sums)
-        dw = dgamma = dbias = None
-        if need_w or need_gamma or need_b:
-            dwp = wgrad16(g, x16, R, S, stride, pad)
-            L = _lib.load()
-            has_bias = conv.bias is not None
-            dgamma = torch.zeros(Cout, device=dy.device, dtype=torch.float32) if need_gamma else None
-            dbias = torch.zeros(Cout, device=dy.device, dtype=torch.float32) if (need_b and has_bias) else None
-            w_tap_major = R * S > 1 and not w.is_contiguous()       # conv._dense(): contiguous or channels-last
-            act16._launch(dy.device, "fi_bn_fold_grad", L.fi_bn_fold_grad, _lib.ptr(dwp), _lib.ptr(w), _lib.ptr(s),
-                          _lib.ptr(scale), _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var), float(bn.eps),
-                          _lib.ptr(conv.bias) if has_bias else None, _lib.ptr(dgamma), _lib.ptr(dbias), Cout, Cin, R * S,
-                          1, 1 if w_tap_major else 0)
-            dw = dwp.permute(0, 3, 1, 2) if need_w else None
-        dx = None
-        if need_x:
-            dx = dgrad16(g, weight_t16(conv, bn, scale, x16.dtype), (x16.shape[2], x16.shape[3]), stride, pad)
-        return (dx, dw, dbias, dgamma, s if need_beta else None, g if (ctx.has_res and need_res) else None,
-                None, None, None, None, None, None)
-
-
 def conv_bn_act16(x16, conv, bn, relu=True, residual=None):
     """act(bn(conv(x16)) [+ residual]) on 16-bit channels-last tensors for use with grad mode ON: the forward is the single
     fi_act16_conv_forward launch of act16.conv_bn_act16 (bit-equal output), the backward three launches of
     libfi_grad16.so and fi_bn_fold_grad.  Gradients: x16 and residual 16-bit channels-last, conv.weight fp32 [Cout, Cin,
     R, S] with channels-last strides (a view of the tap-major buffer), bn.weight / bn.bias (and conv.bias) fp32.  Raises
-    _lib.FiError for a training-mode BatchNorm or a layer fi_act16_conv_eligible / fi_grad16_eligible refuses."""
-    if bn.training or not bn.track_running_stats:
-        raise _lib.FiError("grad16.conv_bn_act16 folds an eval-mode BatchNorm with running statistics; got one in "
-                           "training mode")
-    prec = act16._require_act16(x16, "grad16.conv_bn_act16")
-    _conv._FOLD_PAIRS[bn] = conv
-    fold = _conv._cached_fold(conv, bn)
-    if fold is None:
-        _conv.refresh_bn_folds()
-        fold = _conv._cached_fold(conv, bn)
-    L = load()
-    N, Cin, H, W = x16.shape
-    Cout, _, R, S = conv.weight.shape
-    if N > 0:
-        geom = (N, H, W, Cin, Cout, R, S, conv.stride[0], conv.padding[0])
-        for kind, name in ((WGRAD, "wgrad"), (DGRAD, "dgrad"), (RELU_GRAD, "relu_grad")):
-            _require_eligible(L, "grad16.conv_bn_act16 (%s)" % name, kind, geom, None, None, None, None)
-    return _ConvBnAct16Fn.apply(x16, conv.weight, conv.bias, bn.weight, bn.bias, residual, conv, bn, bool(relu), prec,
-                                fold[0], fold[1])
+    _lib.FiError for a training-mode BatchNorm or a layer fi_act16_conv_eligible / fi_grad16_eligible refuses.
+    This is train16's layer without a hand-off: its output carries a train16.Gate16 that costs nothing unclaimed."""
+    from . import train16          # here: train16 imports this module
+    return train16._layer16("grad16.conv_bn_act16", _dw_permuted, x16, conv, bn, relu, residual, False, None, None, None)
+
+
+def _dw_permuted(dwp, R, S):
+    return dwp.permute(0, 3, 1, 2)          # channels-last strides for a 1x1 layer too

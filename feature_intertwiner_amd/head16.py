@@ -15,7 +15,6 @@ weight copies (step_state.HEAD); stats()['weights'] counts the copies made.  The
 act16.weight16 already keeps there.
 """
 import ctypes
-import os
 
 import torch
 
@@ -25,7 +24,7 @@ from . import conv as _conv
 from . import pyr16 as _pyr16
 from . import step_state as _step_state
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfi_head16.so")
+LIB_PATH = _lib.sublibrary_path("head16")
 _cp, _ci, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 _pp, _ip = ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int)
 _CROP = (_ci, [_pp, _ip, _ip, _ci, _cp, _cp, _cp, _ci, _ci, _ci, _ci, _ci, _cf, _cp, _cp])
@@ -39,7 +38,6 @@ SIGNATURES = {
     "fi_head16_out1x1_bf16": _OUT,
     "fi_head16_out1x1_f16": _OUT,
 }
-_head16 = None
 _STATS = {"crop": 0, "conv": 0, "out": 0, "weights": 0}
 ROWS, SHUFFLE = 0, 1          # out1x1_16's layouts
 NONE, SIGMOID = 0, 1          # ... and activations
@@ -47,20 +45,7 @@ NONE, SIGMOID = 0, 1          # ... and activations
 
 def load():
     """Load libfi_head16.so (after libfi_hip.so, which it links against) and attach the signatures."""
-    global _head16
-    if _head16 is not None:
-        return _head16
-    _lib.load()
-    if not os.path.exists(LIB_PATH):
-        raise _lib.FiError("libfi_head16.so not found at %s -- build it with `python -m feature_intertwiner_amd.build` "
-                           "(there is no CPU/PyTorch fallback)" % LIB_PATH)
-    L = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
-    _head16 = L
-    return L
+    return _lib.load_sublibrary("head16", SIGNATURES)
 
 
 def stats():
@@ -69,8 +54,7 @@ def stats():
 
 
 def reset_stats():
-    for k in _STATS:
-        _STATS[k] = 0
+    _lib.zero_counters(_STATS)
 
 
 def pyramid_crop16_cl(maps16, boxes, box_ind, level, crop_h, crop_w, extrapolation_value=0.0):
@@ -160,17 +144,6 @@ def deconv_weight16(deconv, dtype):
 
 
 # ---- the heads' layers on fi_act16_conv_forward ---------------------------------------------------------------------------
-def _fold(what, conv, bn):
-    if bn.training or not bn.track_running_stats:
-        raise _lib.FiError("%s folds an eval-mode BatchNorm with running statistics; got one in training mode" % what)
-    _conv._FOLD_PAIRS[bn] = conv
-    fold = _conv._cached_fold(conv, bn)
-    if fold is None:
-        _conv.refresh_bn_folds()
-        fold = _conv._cached_fold(conv, bn)
-    return fold
-
-
 def _conv_launch(what, x16, prec, w16, scale, shift, relu, N, H, W, Cin, Cout, R, S, stride, pad):
     """One fi_act16_conv_forward launch, counted in stats()['conv']: y [N, Cout, OH, OW] 16-bit channels-last."""
     A = _act16.load()
@@ -203,7 +176,7 @@ def window_bn_act16(x16, conv, bn, relu=True):
             conv.groups != 1:
         raise _lib.FiError("window_bn_act16: the layer's kernel must be the whole %d x %d map of %d channels without padding "
                            "(weight %s, padding %s)" % (h, w, C, tuple(conv.weight.shape), tuple(conv.padding)))
-    scale, shift = _fold("window_bn_act16", conv, bn)
+    scale, shift = _act16.eval_fold("window_bn_act16", conv, bn)
     w16 = window_weight16(conv.weight, x16.dtype)
     return _conv_launch("window_bn_act16", x16, prec, w16, scale, shift, relu, n, 1, 1, h * w * C, Cout, 1, 1, 1, 0)
 
@@ -219,7 +192,7 @@ def conv_bn_act16(x16, conv, bn, relu=True):
         raise _lib.FiError("conv_bn_act16: the layer must be a dense square-stride convolution of the input's %d channels "
                            "(stride %s, padding %s, dilation %s, groups %d, weight %s)"
                            % (Cin, tuple(stride), tuple(pad), tuple(conv.dilation), conv.groups, tuple(conv.weight.shape)))
-    scale, shift = _fold("conv_bn_act16", conv, bn)
+    scale, shift = _act16.eval_fold("conv_bn_act16", conv, bn)
     w16 = _act16.weight16(conv.weight, x16.dtype)
     return _conv_launch("conv_bn_act16", x16, prec, w16, scale, shift, relu, N, H, W, Cin, Cout, R, S, stride[0], pad[0])
 

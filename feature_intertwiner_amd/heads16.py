@@ -16,7 +16,6 @@ kernels take is decided by fi_heads16_eligible alone; a call it or the other lib
 is no fallback to another path.
 """
 import ctypes
-import os
 
 import torch
 
@@ -30,7 +29,7 @@ from . import head16
 from . import roi16
 from . import train16
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfi_heads16.so")
+LIB_PATH = _lib.sublibrary_path("heads16")
 _cp, _ci = ctypes.c_void_p, ctypes.c_int
 _CROP_BWD = (_ci, [_cp, _cp, _cp, _cp, _ci, _cp, _cp, _cp, _ci, _ci, _ci, _ci, _ci, _ci, _cp])
 _CLASS_ROWS = (_ci, [_cp, _cp, _cp, _cp, _cp, _cp, _cp, _cp, _ci, _ci, _ci, _ci, _ci, _cp])
@@ -43,26 +42,12 @@ SIGNATURES = {
     "fi_heads16_class_rows_backward_f16": _CLASS_ROWS,
 }
 CROP_BWD, CLASS_ROWS = 0, 1          # FI_HEADS16_* kinds of fi_heads16_eligible
-_heads16 = None
 _STATS = {"crop_bwd": 0, "class_rows": 0, "crops": 0}
 
 
 def load():
     """Load libfi_heads16.so (after libfi_hip.so, which it links against) and attach the signatures."""
-    global _heads16
-    if _heads16 is not None:
-        return _heads16
-    _lib.load()
-    if not os.path.exists(LIB_PATH):
-        raise _lib.FiError("libfi_heads16.so not found at %s -- build it with `python -m feature_intertwiner_amd.build` "
-                           "(there is no CPU/PyTorch fallback)" % LIB_PATH)
-    L = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
-    _heads16 = L
-    return L
+    return _lib.load_sublibrary("heads16", SIGNATURES)
 
 
 def stats():
@@ -73,8 +58,7 @@ def stats():
 
 
 def reset_stats():
-    for k in _STATS:
-        _STATS[k] = 0
+    _lib.zero_counters(_STATS)
 
 
 SCOPE = "heads"
@@ -389,17 +373,7 @@ class _Deconv2x2Act16Fn(torch.autograd.Function):
         x16, u, w = ctx.saved_tensors
         need_x, need_w, need_b = ctx.needs_input_grad[:3]
         cin, cout = w.shape[0], w.shape[1]
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        g = s = None
-        if ctx.out_gate is not None and ctx.out_gate.claimed:
-            s = ctx.out_gate.take(dy)
-            if s is not None:
-                g = dy
-                train16._STATS["premasked"] += 1
-            else:
-                train16._STATS["fallback"] += 1
-        if g is None:
-            g, s = grad16.relu_grad16(dy, u, relu=True, colsum=need_b)
+        g, s = train16.masked_grad16(dy, u, ctx.out_gate, True, need_b)
         dw = db = dx = None
         if need_w:
             dwp = grad16.wgrad16(g, x16, 1, 1, 1, 0)                    # [4 Cout, 1, 1, Cin], rows (a, b, co)
@@ -407,13 +381,7 @@ class _Deconv2x2Act16Fn(torch.autograd.Function):
         if need_b:
             db = s.view(4, cout).sum(0)
         if need_x:
-            wt = deconv_weight_t16(ctx.deconv, x16.dtype)
-            hw = (x16.shape[2], x16.shape[3])
-            if ctx.in_gate is not None:
-                dx, s_in = train16.dgrad_gated16(g, wt, x16, hw, 1, 0, colsum=True)
-                ctx.in_gate.leave(dx, s_in)
-            else:
-                dx = grad16.dgrad16(g, wt, hw, 1, 0)
+            dx = train16.data_grad16(g, deconv_weight_t16(ctx.deconv, x16.dtype), x16, ctx.in_gate, 1, 0)
         return dx, dw, db, None, None, None
 
 
@@ -430,18 +398,9 @@ def deconv2x2_bias_act16(x16, deconv, gate_dx=False):
     N, Cin, H, W = x16.shape
     cout = deconv.weight.shape[1]
     in_gate = train16._claim_gate16(x16, gate_dx)
-    if N > 0:
-        geom = (N, H, W, Cin, 4 * cout, 1, 1, 1, 0)
-        L = grad16.load()
-        for kind, name in ((grad16.WGRAD, "wgrad"), (grad16.DGRAD, "dgrad"), (grad16.RELU_GRAD, "relu_grad")):
-            grad16._require_eligible(L, "deconv2x2_bias_act16 (%s)" % name, kind, geom, None, None, None, None)
-        if in_gate is not None and train16.load().fi_train16_eligible(*geom, None, None, None, None) != 1:
-            raise _lib.FiError("deconv2x2_bias_act16: fi_train16_eligible refuses this layer %s; there is no fallback" % (geom,))
-    out_gate = train16.Gate16() if torch.is_grad_enabled() else None
-    u = _Deconv2x2Act16Fn.apply(x16, deconv.weight, deconv.bias, deconv, in_gate, out_gate)
-    if out_gate is not None:
-        u._fi_gate16 = out_gate
-    return u
+    train16.require_backward16("deconv2x2_bias_act16", (N, H, W, Cin, 4 * cout, 1, 1, 1, 0), True, in_gate)
+    return train16.with_out_gate16(True, lambda out_gate: _Deconv2x2Act16Fn.apply(x16, deconv.weight, deconv.bias, deconv,
+                                                                                  in_gate, out_gate))
 
 
 # ---- the box head's layers ----------------------------------------------------------------------------------------------
@@ -478,33 +437,14 @@ class _WindowBnAct16Fn(torch.autograd.Function):
         conv, bn = ctx.conv, ctx.bn
         need_x, need_w, need_b, need_gamma, need_beta = ctx.needs_input_grad[:5]
         Cout, Cin, R, S = w.shape
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        g = s = None
-        if ctx.out_gate is not None and ctx.out_gate.claimed:
-            s = ctx.out_gate.take(dy)
-            if s is not None:
-                g = dy
-                train16._STATS["premasked"] += 1
-            else:
-                train16._STATS["fallback"] += 1
-        if g is None:
-            g, s = grad16.relu_grad16(dy, y, relu=True, colsum=True)
+        g, s = train16.masked_grad16(dy, y, ctx.out_gate, True, True)
         xv = _rows_view(x16)
-        dw = dgamma = dbias = None
-        if need_w or need_gamma or need_b:
-            dwp = grad16.wgrad16(g, xv, 1, 1, 1, 0)                  # [Cout, 1, 1, R S Cin]: tap-major
-            has_bias = conv.bias is not None
-            dgamma = torch.zeros(Cout, device=dy.device, dtype=torch.float32) if need_gamma else None
-            dbias = torch.zeros(Cout, device=dy.device, dtype=torch.float32) if (need_b and has_bias) else None
-            act16._launch(dy.device, "fi_bn_fold_grad", _lib.load().fi_bn_fold_grad, _lib.ptr(dwp), _lib.ptr(w), _lib.ptr(s),
-                          _lib.ptr(scale), _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var), float(bn.eps),
-                          _lib.ptr(conv.bias) if has_bias else None, _lib.ptr(dgamma), _lib.ptr(dbias), Cout, Cin, R * S,
-                          1, 0 if w.is_contiguous() else 1)
-            if need_w:
-                dw = dwp.view(Cout, R, S, Cin).permute(0, 3, 1, 2)   # the channels-last view of the tap-major buffer
+        # dW' [Cout, 1, 1, R S Cin] is tap-major: its [Cout, R, S, Cin] view goes through the 3x3 layers' channels-last view
+        dwp, dgamma, dbias = train16.fold_weight_grad16(g, xv, w, conv, bn, scale, s, 1, 1, 1, 0, need_w, need_gamma, need_b)
+        dw = train16.dw_view16(dwp.view(Cout, R, S, Cin), R, S) if need_w else None
         dx = None
         if need_x:
-            dxv = grad16.dgrad16(g, window_weight_t16(conv, bn, scale, x16.dtype), (1, 1), 1, 0)
+            dxv = train16.data_grad16(g, window_weight_t16(conv, bn, scale, x16.dtype), xv, None, 1, 0)
             dx = dxv.view(x16.shape[0], R, S, Cin).permute(0, 3, 1, 2)
         return dx, dw, dbias, dgamma, s if need_beta else None, None, None, None, None
 
@@ -513,30 +453,17 @@ def window_bn_act16(x16, conv, bn):
     """head16.window_bn_act16 (relu(bn(conv(x16))) for a kernel that is the whole map, [n, Cout, 1, 1]) with grad mode ON:
     the same launch, bit-equal output, which carries a train16.Gate16.  The weight gradient has the channels-last strides
     of the tap-major buffer.  Raises _lib.FiError for what the eligibility queries refuse; there is no fallback."""
-    if bn.training or not bn.track_running_stats:
-        raise _lib.FiError("heads16.window_bn_act16 folds an eval-mode BatchNorm with running statistics; got one in "
-                           "training mode")
+    act16.require_eval_bn("heads16.window_bn_act16", bn)
     act16._require_act16(x16, "heads16.window_bn_act16")
-    _conv._FOLD_PAIRS[bn] = conv
-    fold = _conv._cached_fold(conv, bn)
-    if fold is None:
-        _conv.refresh_bn_folds()
-        fold = _conv._cached_fold(conv, bn)
+    fold = act16.eval_fold("heads16.window_bn_act16", conv, bn)
     n, C, h, w = x16.shape
     Cout = conv.weight.shape[0]
     if tuple(conv.weight.shape[1:]) != (C, h, w):
         raise _lib.FiError("heads16.window_bn_act16: the layer's kernel must be the whole %d x %d map of %d channels (weight "
                            "%s)" % (h, w, C, tuple(conv.weight.shape)))
-    if n > 0:
-        geom = (n, 1, 1, h * w * C, Cout, 1, 1, 1, 0)
-        L = grad16.load()
-        for kind, name in ((grad16.WGRAD, "wgrad"), (grad16.DGRAD, "dgrad"), (grad16.RELU_GRAD, "relu_grad")):
-            grad16._require_eligible(L, "heads16.window_bn_act16 (%s)" % name, kind, geom, None, None, None, None)
-    out_gate = train16.Gate16() if torch.is_grad_enabled() else None
-    y = _WindowBnAct16Fn.apply(x16, conv.weight, conv.bias, bn.weight, bn.bias, conv, bn, fold[0], out_gate)
-    if out_gate is not None:
-        y._fi_gate16 = out_gate
-    return y
+    train16.require_backward16("heads16.window_bn_act16", (n, 1, 1, h * w * C, Cout, 1, 1, 1, 0))
+    return train16.with_out_gate16(True, lambda out_gate: _WindowBnAct16Fn.apply(x16, conv.weight, conv.bias, bn.weight,
+                                                                                 bn.bias, conv, bn, fold[0], out_gate))
 
 
 def stacked_linear_t16(linears, dtype):
@@ -581,12 +508,7 @@ class _StackedOut16Fn(torch.autograd.Function):
         g = g.view(n, Kp, 1, 1)
         dx = None
         if ctx.needs_input_grad[0]:
-            wt = ctx.wt()
-            if ctx.in_gate is not None:
-                dx, s_in = train16.dgrad_gated16(g, wt, x16, (x16.shape[2], x16.shape[3]), 1, 0, colsum=True)
-                ctx.in_gate.leave(dx, s_in)
-            else:
-                dx = grad16.dgrad16(g, wt, (x16.shape[2], x16.shape[3]), 1, 0)
+            dx = train16.data_grad16(g, ctx.wt(), x16, ctx.in_gate, 1, 0)
         need = ctx.needs_input_grad[3:]
         dwp = grad16.wgrad16(g, x16, 1, 1, 1, 0).view(Kp, Cin) if any(need[0::2]) else None
         db = d.sum(0) if any(need[1::2]) else None
@@ -611,13 +533,7 @@ def stacked_out16(x16, linears, gate_dx=False):
                            % (tuple(x16.shape),))
     K = sum(l.weight.shape[0] for l in linears)
     in_gate = train16._claim_gate16(x16, gate_dx)
-    if n > 0:
-        geom = (n, 1, 1, Cin, (K + 31) // 32 * 32, 1, 1, 1, 0)
-        L = grad16.load()
-        for kind, name in ((grad16.WGRAD, "wgrad"), (grad16.DGRAD, "dgrad")):
-            grad16._require_eligible(L, "stacked_out16 (%s)" % name, kind, geom, None, None, None, None)
-        if in_gate is not None and train16.load().fi_train16_eligible(*geom, None, None, None, None) != 1:
-            raise _lib.FiError("stacked_out16: fi_train16_eligible refuses this layer %s; there is no fallback" % (geom,))
+    train16.require_backward16("stacked_out16", (n, 1, 1, Cin, (K + 31) // 32 * 32, 1, 1, 1, 0), False, in_gate)
     params = []
     for l in linears:
         params += [l.weight, l.bias]

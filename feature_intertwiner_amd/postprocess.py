@@ -7,7 +7,6 @@ kernels are in csrc/unmold.hip; this module only allocates, scans the per-detect
 One host synchronisation reads the sizes (the results go to the host anyway).  `coco_results` builds the
 reference's result dicts (lib/workflow.py:405-413)."""
 import ctypes
-import os
 
 import numpy as np
 import torch
@@ -15,7 +14,7 @@ import torch
 from . import _lib
 from ._lib import FiError, check, current_stream, ptr, require_cuda
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfi_eval.so")
+LIB_PATH = _lib.sublibrary_path("eval")
 _p, _i, _ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
 # name -> (restype, argtypes); mirrors include/fi_eval.h one to one
 SIGNATURES = {
@@ -24,25 +23,11 @@ SIGNATURES = {
     "fi_unmold_encode": (_i, [_p] * 4 + [_i] * 4 + [_p] * 4 + [_p]),
     "fi_unmold_paste": (_i, [_p] * 4 + [_i] * 4 + [_p, _ll, _p, _p]),
 }
-_eval = None
 
 
 def load():
     """Load libfi_eval.so (after libfi_hip.so, which it links against) and attach the signatures."""
-    global _eval
-    if _eval is not None:
-        return _eval
-    _lib.load()
-    if not os.path.exists(LIB_PATH):
-        raise FiError("libfi_eval.so not found at %s -- build it with `python -m feature_intertwiner_amd.build` "
-                      "(there is no CPU/PyTorch fallback)" % LIB_PATH)
-    L = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
-    _eval = L
-    return L
+    return _lib.load_sublibrary("eval", SIGNATURES)
 
 
 def _host_int32(x, cols):

@@ -7,7 +7,6 @@ decided by fi_pyr16_lateral_eligible / fi_pyr16_head1x1_eligible alone; nothing 
 refuse is an error -- there is no fallback to another path.
 """
 import ctypes
-import os
 
 import torch
 
@@ -15,7 +14,7 @@ from . import _lib
 from . import act16 as _act16
 from . import conv as _conv
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfi_pyr16.so")
+LIB_PATH = _lib.sublibrary_path("pyr16")
 _cp, _ci = ctypes.c_void_p, ctypes.c_int
 _LATERAL = (_ci, [_cp, _cp, _cp, _cp, _cp, _ci, _ci, _ci, _ci, _ci, _cp])
 _HEAD = (_ci, [_cp, _cp, _cp, _cp, _ci, _ci, _ci, _ci, _ci, _cp])
@@ -28,27 +27,13 @@ SIGNATURES = {
     "fi_pyr16_head1x1_bf16": _HEAD,
     "fi_pyr16_head1x1_f16": _HEAD,
 }
-_pyr16 = None
 _STATS = {"lateral": 0, "head": 0}
 SCOPES = ("trunk", "pyramid", "roi", "detect")
 
 
 def load():
     """Load libfi_pyr16.so (after libfi_hip.so, which it links against) and attach the signatures."""
-    global _pyr16
-    if _pyr16 is not None:
-        return _pyr16
-    _lib.load()
-    if not os.path.exists(LIB_PATH):
-        raise _lib.FiError("libfi_pyr16.so not found at %s -- build it with `python -m feature_intertwiner_amd.build` "
-                           "(there is no CPU/PyTorch fallback)" % LIB_PATH)
-    L = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
-    _pyr16 = L
-    return L
+    return _lib.load_sublibrary("pyr16", SIGNATURES)
 
 
 def stats():
@@ -57,8 +42,7 @@ def stats():
 
 
 def reset_stats():
-    for k in _STATS:
-        _STATS[k] = 0
+    _lib.zero_counters(_STATS)
 
 
 def act_scope(model_cfg):

@@ -6,7 +6,6 @@ fi_pyramid_crop_forward_nhwc on the widened maps.  Which calls the kernel takes 
 alone; nothing here restates its rules, and a call it refuses is an error -- there is no fallback to another path.
 """
 import ctypes
-import os
 
 import torch
 
@@ -15,7 +14,7 @@ from . import act16 as _act16
 from . import conv as _conv
 from . import pyr16 as _pyr16
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfi_roi16.so")
+LIB_PATH = _lib.sublibrary_path("roi16")
 _cp, _ci, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 _pp, _ip = ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int)
 _CROP = (_ci, [_pp, _ip, _ip, _ci, _cp, _cp, _cp, _ci, _ci, _ci, _ci, _ci, _cf, _cp, _cp])
@@ -25,26 +24,12 @@ SIGNATURES = {
     "fi_roi16_pyramid_crop_forward_bf16": _CROP,
     "fi_roi16_pyramid_crop_forward_f16": _CROP,
 }
-_roi16 = None
 _STATS = {"crop": 0}
 
 
 def load():
     """Load libfi_roi16.so (after libfi_hip.so, which it links against) and attach the signatures."""
-    global _roi16
-    if _roi16 is not None:
-        return _roi16
-    _lib.load()
-    if not os.path.exists(LIB_PATH):
-        raise _lib.FiError("libfi_roi16.so not found at %s -- build it with `python -m feature_intertwiner_amd.build` "
-                           "(there is no CPU/PyTorch fallback)" % LIB_PATH)
-    L = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
-    _roi16 = L
-    return L
+    return _lib.load_sublibrary("roi16", SIGNATURES)
 
 
 def stats():
@@ -53,8 +38,7 @@ def stats():
 
 
 def reset_stats():
-    for k in _STATS:
-        _STATS[k] = 0
+    _lib.zero_counters(_STATS)
 
 
 def pyramid_crop16(maps16, boxes, box_ind, level, crop_h, crop_w, extrapolation_value=0.0):

@@ -3,17 +3,20 @@ libfi_train16.so (include/fi_train16.h, csrc/conv_train16.hip) as a thin wrapper
 `conv_bn_act16` with the gradient hand-offs of the fp32 path (conv.GradBox) and the differentiable boundary casts
 `pack` / `unpack`.
 
-The forward of a layer is act16's single fi_act16_conv_forward launch.  Its backward is grad16's (relu_grad16, wgrad16,
-fi_bn_fold_grad, dgrad16) with two changes: gradients can travel through GradBoxes instead of autograd, and a consumer
-that sees the whole gradient of its input runs the GATED data gradient -- one launch that applies the producing layer's
-ReLU mask and leaves that layer's column sums on its Gate16, so the producer runs no relu_grad16 at all.
+The forward of a layer is act16's single fi_act16_conv_forward launch.  Its backward is grad16's operators (relu_grad16,
+wgrad16, fi_bn_fold_grad, dgrad16) with two changes: gradients can travel through GradBoxes instead of autograd, and a
+consumer that sees the whole gradient of its input runs the GATED data gradient -- one launch that applies the producing
+layer's ReLU mask and leaves that layer's column sums on its Gate16, so the producer runs no relu_grad16 at all.
+
+The steps of that backward are written here once -- require_backward16, with_out_gate16, masked_grad16,
+fold_weight_grad16, dw_view16, data_grad16 -- and the layers of fpn16 and heads16 call them; grad16.conv_bn_act16 is this
+module's layer without a hand-off.
 
 Plain allocations: the gradient arena and the deferred / batched weight-gradient queues of the fp32 path are not wired.
 Which layers the kernels take is decided by fi_train16_eligible / fi_grad16_eligible alone; a layer they refuse is an
 error -- there is no fallback to another path.
 """
 import ctypes
-import os
 
 import torch
 
@@ -22,7 +25,7 @@ from . import act16
 from . import conv as _conv
 from . import grad16
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfi_train16.so")
+LIB_PATH = _lib.sublibrary_path("train16")
 _cp, _ci = ctypes.c_void_p, ctypes.c_int
 _GATED = (_ci, [_cp, _cp, _cp, _cp, _cp, _cp, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _cp])
 # name -> (restype, argtypes); mirrors include/fi_train16.h one to one
@@ -31,27 +34,13 @@ SIGNATURES = {
     "fi_train16_conv_dgrad_gated_bf16": _GATED,
     "fi_train16_conv_dgrad_gated_f16": _GATED,
 }
-_train16 = None
 _STATS = {"gated": 0, "premasked": 0, "fallback": 0, "pack": 0, "unpack": 0}
 _PAIR_ADDS = [0]
 
 
 def load():
     """Load libfi_train16.so (after libfi_hip.so, which it links against) and attach the signatures."""
-    global _train16
-    if _train16 is not None:
-        return _train16
-    _lib.load()
-    if not os.path.exists(LIB_PATH):
-        raise _lib.FiError("libfi_train16.so not found at %s -- build it with `python -m feature_intertwiner_amd.build` "
-                           "(there is no CPU/PyTorch fallback)" % LIB_PATH)
-    L = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
-    _train16 = L
-    return L
+    return _lib.load_sublibrary("train16", SIGNATURES)
 
 
 def stats():
@@ -64,8 +53,7 @@ def stats():
 
 
 def reset_stats():
-    for k in _STATS:
-        _STATS[k] = 0
+    _lib.zero_counters(_STATS)
     _PAIR_ADDS[0] = 0
 
 
@@ -192,21 +180,100 @@ def _take_boxes16(boxes):
     return out.contiguous(memory_format=torch.channels_last)
 
 
+# ---- the steps every 16-bit layer backward shares (this module's layer, fpn16's and heads16's) ----------------------------
+_KINDS = ((grad16.WGRAD, "wgrad"), (grad16.DGRAD, "dgrad"), (grad16.RELU_GRAD, "relu_grad"))
+
+
+def require_backward16(what, geom, relu=True, in_gate=None):
+    """The eligibility preamble of a layer with geom = (N, H, W, Cin, Cout, R, S, stride, pad): _lib.FiError, prefixed
+    `what`, unless fi_grad16_eligible takes its weight and data gradient (and its ReLU mask when `relu`) and, when the
+    layer claimed its input's gate, fi_train16_eligible the gated launch.  An empty batch launches nothing: no query."""
+    if geom[0] <= 0:
+        return
+    L = grad16.load()
+    for kind, name in (_KINDS if relu else _KINDS[:2]):
+        grad16._require_eligible(L, "%s (%s)" % (what, name), kind, geom, None, None, None, None)
+    if in_gate is not None and load().fi_train16_eligible(*geom, None, None, None, None) != 1:
+        raise _lib.FiError("%s: fi_train16_eligible refuses this layer %s; there is no fallback" % (what, geom))
+
+
+def with_out_gate16(relu, apply):
+    """y = apply(gate) with gate a new Gate16, hung on y as `_fi_gate16`, for a layer with a ReLU while a graph is
+    recorded; apply(None) otherwise."""
+    gate = Gate16() if (relu and torch.is_grad_enabled()) else None
+    y = apply(gate)
+    if gate is not None:
+        y._fi_gate16 = gate
+    return y
+
+
+def masked_grad16(dy, y, out_gate, relu, want_sums):
+    """(g, s) with g = dy * (y > 0) and s = sum_p g: dy itself and the sums on `out_gate` when the gate was claimed and
+    its claimer wrote this very dy (counted 'premasked'); else one relu_grad16 launch -- counted 'fallback' when the gate
+    WAS claimed: masking a masked gradient again is idempotent and recomputes the sums.  dy as autograd delivers it."""
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    if out_gate is not None and out_gate.claimed:
+        s = out_gate.take(dy)
+        if s is not None:
+            _STATS["premasked"] += 1
+            return dy, s
+        _STATS["fallback"] += 1
+    return grad16.relu_grad16(dy, y, relu=relu, colsum=want_sums)
+
+
+def fold_weight_grad16(g, x_rows, w, conv, bn, scale, s, R, S, stride, pad, need_w, need_gamma, need_b):
+    """(dW, d gamma, d conv.bias) of a layer behind the folded eval-mode `bn`: dW' = wgrad16 of the UNSCALED g on x_rows
+    as an R x S layer, then ONE fi_bn_fold_grad launch: dW = scale * dW' in place, d gamma = inv_std (<W, dW'> +
+    (conv_bias - mean) s), d conv_bias = scale * s.  dW is the tap-major buffer [Cout, R, S, Cin]: the caller views it
+    (dw_view16).  All None when none of the three is needed."""
+    if not (need_w or need_gamma or need_b):
+        return None, None, None
+    dwp = grad16.wgrad16(g, x_rows, R, S, stride, pad)
+    Cout, Cin, taps = w.shape[0], w.shape[1], w.shape[2] * w.shape[3]
+    has_bias = conv.bias is not None
+    dgamma = torch.zeros(Cout, device=g.device, dtype=torch.float32) if need_gamma else None
+    dbias = torch.zeros(Cout, device=g.device, dtype=torch.float32) if (need_b and has_bias) else None
+    w_tap_major = taps > 1 and not w.is_contiguous()       # conv._dense(): contiguous or channels-last
+    act16._launch(g.device, "fi_bn_fold_grad", _lib.load().fi_bn_fold_grad, _lib.ptr(dwp), _lib.ptr(w), _lib.ptr(s),
+                  _lib.ptr(scale), _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var), float(bn.eps),
+                  _lib.ptr(conv.bias) if has_bias else None, _lib.ptr(dgamma), _lib.ptr(dbias), Cout, Cin, taps,
+                  1, 1 if w_tap_major else 0)
+    return dwp, dgamma, dbias
+
+
+def dw_view16(dwp, R, S):
+    """The tap-major weight gradient with the strides of its parameter: [Cout, Cin, 1, 1] contiguous for a 1x1 layer,
+    channels-last strides for a 3x3 one (what prepare_step gives the weight; optim.clip_and_step wants gradient and
+    parameter to share their strides, and autograd re-lays a gradient that does not)."""
+    Cout, _, _, Cin = dwp.shape
+    return dwp.view(Cout, Cin, 1, 1) if R * S == 1 else dwp.permute(0, 3, 1, 2)
+
+
+def data_grad16(g, wt, x16, in_gate, stride, pad, dx_add=None):
+    """dx of g on the data-gradient operand wt, like x16: the gated launch, which leaves dx and the producer's column
+    sums on `in_gate`, when the layer claimed its input's gate; dgrad16 otherwise."""
+    hw = (x16.shape[2], x16.shape[3])
+    if in_gate is None:
+        return grad16.dgrad16(g, wt, hw, stride, pad, dx_add=dx_add)
+    dx, s_in = dgrad_gated16(g, wt, x16, hw, stride, pad, dx_add=dx_add, colsum=True)
+    in_gate.leave(dx, s_in)
+    return dx
+
+
 class _ConvBnAct16Fn(torch.autograd.Function):
-    """grad16._ConvBnAct16Fn with the hand-offs of conv._ConvBnActFn.  Backward, with g = dy * (y > 0): g and s = sum_p g
-    come from the Gate16 of y when its claimer wrote this very dy (premasked), else from relu_grad16; dW' = wgrad16 of the
-    UNSCALED g and fi_bn_fold_grad exactly as in grad16; the shortcut gradient g goes to `res_grad_to` or to autograd; dx
-    = the data gradient of g on the SCALED weight plus what `dx_add_from` holds -- the gated launch when this layer claimed
-    its input's gate, dgrad16 otherwise -- and goes to `dx_give_to` or to autograd."""
+    """y = act(conv(x16, W) * scale + shift (+ residual)), scale / shift the eval-BatchNorm fold, with the hand-offs of
+    conv._ConvBnActFn.  Backward: g and s from masked_grad16; dW, d gamma and d conv.bias from fold_weight_grad16, d beta
+    = s; the shortcut gradient g goes to `res_grad_to` or to autograd; dx = data_grad16 of g on the SCALED weight plus
+    what `dx_add_from` holds, and goes to `dx_give_to` or to autograd."""
 
     @staticmethod
     def forward(ctx, x16, weight, bias, gamma, beta, residual, conv, bn, relu, prec, scale, shift, res_grad_to,
-                dx_add_from, dx_give_to, in_gate, out_gate):
-        y = act16._conv16("train16.conv_bn_act16", x16, prec, conv, scale, shift, relu, residual)
+                dx_add_from, dx_give_to, in_gate, out_gate, what, dw_view):
+        y = act16._conv16(what, x16, prec, conv, scale, shift, relu, residual)
         ctx.save_for_backward(x16, y, weight, scale)
         ctx.conv, ctx.bn, ctx.relu, ctx.has_res = conv, bn, relu, residual is not None
         ctx.res_grad_to, ctx.dx_add_from, ctx.dx_give_to = res_grad_to, dx_add_from, dx_give_to
-        ctx.in_gate, ctx.out_gate = in_gate, out_gate
+        ctx.in_gate, ctx.out_gate, ctx.dw_view = in_gate, out_gate, dw_view
         return y
 
     @staticmethod
@@ -214,38 +281,11 @@ class _ConvBnAct16Fn(torch.autograd.Function):
         x16, y, w, scale = ctx.saved_tensors
         conv, bn = ctx.conv, ctx.bn
         need_x, need_w, need_b, need_gamma, need_beta, need_res = ctx.needs_input_grad[:6]
-        Cout, Cin, R, S = w.shape
+        R, S = w.shape[2], w.shape[3]
         stride, pad = conv.stride[0], conv.padding[0]
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        want_sums = need_w or need_b or need_gamma or need_beta
-        g = s = None
-        claimed = ctx.out_gate is not None and ctx.out_gate.claimed
-        if claimed:
-            s = ctx.out_gate.take(dy)
-            if s is not None:
-                g = dy
-                _STATS["premasked"] += 1
-            else:
-                _STATS["fallback"] += 1      # masking a masked gradient again is idempotent and recomputes the sums
-        if g is None:
-            g, s = grad16.relu_grad16(dy, y, relu=ctx.relu, colsum=want_sums)
-        dw = dgamma = dbias = None
-        if need_w or need_gamma or need_b:
-            dwp = grad16.wgrad16(g, x16, R, S, stride, pad)
-            L = _lib.load()
-            has_bias = conv.bias is not None
-            dgamma = torch.zeros(Cout, device=dy.device, dtype=torch.float32) if need_gamma else None
-            dbias = torch.zeros(Cout, device=dy.device, dtype=torch.float32) if (need_b and has_bias) else None
-            w_tap_major = R * S > 1 and not w.is_contiguous()       # conv._dense(): contiguous or channels-last
-            act16._launch(dy.device, "fi_bn_fold_grad", L.fi_bn_fold_grad, _lib.ptr(dwp), _lib.ptr(w), _lib.ptr(s),
-                          _lib.ptr(scale), _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var), float(bn.eps),
-                          _lib.ptr(conv.bias) if has_bias else None, _lib.ptr(dgamma), _lib.ptr(dbias), Cout, Cin, R * S,
-                          1, 1 if w_tap_major else 0)
-            if need_w:
-                # a view of the tap-major buffer with the strides of the parameter: [Cout, Cin, 1, 1] contiguous for a 1x1
-                # layer, channels-last strides for a 3x3 one (what prepare_step gives the weight; optim.clip_and_step
-                # wants gradient and parameter to share their strides, and autograd re-lays a gradient that does not)
-                dw = dwp.view(Cout, Cin, 1, 1) if R * S == 1 else dwp.permute(0, 3, 1, 2)
+        g, s = masked_grad16(dy, y, ctx.out_gate, ctx.relu, need_w or need_b or need_gamma or need_beta)
+        dwp, dgamma, dbias = fold_weight_grad16(g, x16, w, conv, bn, scale, s, R, S, stride, pad, need_w, need_gamma, need_b)
+        dw = ctx.dw_view(dwp, R, S) if need_w else None
         g_res = g if (ctx.has_res and need_res) else None
         if g_res is not None and ctx.res_grad_to is not None:
             ctx.res_grad_to.value = g_res           # picked up by the block's first convolution
@@ -253,17 +293,11 @@ class _ConvBnAct16Fn(torch.autograd.Function):
         add = _take_boxes16(ctx.dx_add_from)
         dx = None
         if need_x:
-            wt = grad16.weight_t16(conv, bn, scale, x16.dtype)
-            hw = (x16.shape[2], x16.shape[3])
-            if ctx.in_gate is not None:
-                dx, s_in = dgrad_gated16(g, wt, x16, hw, stride, pad, dx_add=add, colsum=True)
-                ctx.in_gate.leave(dx, s_in)
-            else:
-                dx = grad16.dgrad16(g, wt, hw, stride, pad, dx_add=add)
+            dx = data_grad16(g, grad16.weight_t16(conv, bn, scale, x16.dtype), x16, ctx.in_gate, stride, pad, dx_add=add)
             if ctx.dx_give_to is not None:
                 ctx.dx_give_to.value = dx           # picked up (and added) by the backward of the block's first conv
                 dx = None
-        return (dx, dw, dbias, dgamma, s if need_beta else None, g_res) + (None,) * 11
+        return (dx, dw, dbias, dgamma, s if need_beta else None, g_res) + (None,) * 13
 
 
 def conv_bn_act16(x16, conv, bn, relu=True, residual=None, gate_dx=False, dx_add_from=None, res_grad_to=None,
@@ -280,32 +314,23 @@ def conv_bn_act16(x16, conv, bn, relu=True, residual=None, gate_dx=False, dx_add
     as Bottleneck does -- that costs one more 16-bit rounding of the chained value and no pass.
     The givers must run first in backward: apply them AFTER the taker in forward (conv.GradBox).
     Raises _lib.FiError for a CPU tensor, a training-mode BatchNorm or a layer the eligibility queries refuse."""
-    if bn.training or not bn.track_running_stats:
-        raise _lib.FiError("train16.conv_bn_act16 folds an eval-mode BatchNorm with running statistics; got one in "
-                           "training mode")
-    prec = act16._require_act16(x16, "train16.conv_bn_act16")
-    _conv._FOLD_PAIRS[bn] = conv
-    fold = _conv._cached_fold(conv, bn)
-    if fold is None:
-        _conv.refresh_bn_folds()
-        fold = _conv._cached_fold(conv, bn)
-    L = grad16.load()
+    return _layer16("train16.conv_bn_act16", dw_view16, x16, conv, bn, relu, residual, gate_dx, dx_add_from, res_grad_to,
+                    dx_give_to)
+
+
+def _layer16(what, dw_view, x16, conv, bn, relu, residual, gate_dx, dx_add_from, res_grad_to, dx_give_to):
+    """conv_bn_act16 under the caller's name `what`, the weight gradient viewed by dw_view(dwp, R, S): the one
+    differentiable conv + eval-BatchNorm + ReLU layer (grad16.conv_bn_act16 is this without a hand-off)."""
+    act16.require_eval_bn(what, bn)               # the order of the refusals: the BatchNorm, the tensor, then the lookup
+    prec = act16._require_act16(x16, what)
+    fold = act16.eval_fold(what, conv, bn)
     N, Cin, H, W = x16.shape
     Cout, _, R, S = conv.weight.shape
     in_gate = _claim_gate16(x16, gate_dx)
-    if N > 0:
-        geom = (N, H, W, Cin, Cout, R, S, conv.stride[0], conv.padding[0])
-        for kind, name in ((grad16.WGRAD, "wgrad"), (grad16.DGRAD, "dgrad"), (grad16.RELU_GRAD, "relu_grad")):
-            grad16._require_eligible(L, "train16.conv_bn_act16 (%s)" % name, kind, geom, None, None, None, None)
-        if in_gate is not None and load().fi_train16_eligible(*geom, None, None, None, None) != 1:
-            raise _lib.FiError("train16.conv_bn_act16: fi_train16_eligible refuses this layer %s; there is no fallback"
-                               % (geom,))
-    out_gate = Gate16() if (relu and torch.is_grad_enabled()) else None
-    y = _ConvBnAct16Fn.apply(x16, conv.weight, conv.bias, bn.weight, bn.bias, residual, conv, bn, bool(relu), prec,
-                             fold[0], fold[1], res_grad_to, dx_add_from, dx_give_to, in_gate, out_gate)
-    if out_gate is not None:
-        y._fi_gate16 = out_gate
-    return y
+    require_backward16(what, (N, H, W, Cin, Cout, R, S, conv.stride[0], conv.padding[0]), True, in_gate)
+    return with_out_gate16(relu, lambda out_gate: _ConvBnAct16Fn.apply(
+        x16, conv.weight, conv.bias, bn.weight, bn.bias, residual, conv, bn, bool(relu), prec, fold[0], fold[1],
+        res_grad_to, dx_add_from, dx_give_to, in_gate, out_gate, what, dw_view))
 
 
 class _PackFn(torch.autograd.Function):

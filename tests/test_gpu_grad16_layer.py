@@ -271,3 +271,52 @@ def test_three_layer_bottleneck_runs_and_every_backward_launch_replays_within_th
             ref = R.dgrad_ref(g, w_l, (stride, stride), (pad, pad), in_hw)
             B = _B(wt.shape[3] * k * k, R.dgrad_ref(g.abs(), w_l.abs(), (stride, stride), (pad, pad), in_hw))
             _held(out, ref, B + UNIT[sfx] * (ref.abs() + B) + SUBNORMAL[sfx], "replay dgrad %dx%d" % (k, k))
+
+
+# N 2 on 2 x 3, 32 channels: the fewest channels fi_grad16_eligible takes for all three kinds (tests/test_grad16_host.py), an
+# odd map smaller than every tile, and 12 pixels, at which every gradient is the same bits on every run, so that torch.equal
+# can be asked of all of them:
+#   dW       wgrad16 adds with atomics only once it splits its pixel range, from 1024 pixels on (csrc/conv_grad16.hip,
+#            wgrad_split);
+#   the sums relu_grad16 adds its threads' partial column sums with atomics in LDS; at 32 channels the threads of its first
+#            wave hold rows 0 .. 15 and every other wave adds exact zeros, so up to 16 pixels the order of the adds is that of
+#            the lanes of one instruction (at 5 x 7 the last bits of d beta, d gamma and d conv.bias differ between two runs of
+#            the SAME layer function).
+ONE_PATH = [(2, 2, 3, 32, 32, 1, 1), (2, 2, 3, 32, 32, 3, 1)]
+
+
+@pytest.mark.parametrize("sfx", sorted(DTYPES))
+@pytest.mark.parametrize("with_res", [False, True], ids=["plain", "residual"])
+@pytest.mark.parametrize("shape", ONE_PATH, ids=_ids)
+def test_grad16_layer_is_the_train16_layer_without_a_hand_off(shape, with_res, sfx):
+    """grad16.conv_bn_act16 and train16.conv_bn_act16 with no hand-off are one code path: the same bits in y and in every
+    gradient, the same launches, and no gate traffic -- the Gate16 on the output is never claimed."""
+    from feature_intertwiner_amd import grad16, train16
+    N, H, W, Cin, Cout, k, stride = shape
+    dtype = DTYPES[sfx]
+    gen = torch.Generator().manual_seed(40 + sum(shape))
+    x0 = _act((N, Cin, H, W), dtype, gen).detach()
+    res0 = _act((N, Cout, H, W), dtype, gen).detach() if with_res else None
+    dy = torch.randn((N, Cout, H, W), generator=gen).to(dtype).to(DEV).contiguous(memory_format=CL)
+    train16.reset_stats()
+    out = {}
+    for name, layer in (("grad16", grad16.conv_bn_act16), ("train16", train16.conv_bn_act16)):
+        conv, bn = _layer(Cin, Cout, k, stride, seed=sum(shape))
+        x16 = x0.clone().requires_grad_()
+        res = res0.clone().requires_grad_() if with_res else None
+        y = layer(x16, conv, bn, relu=True, residual=res)
+        assert 0 < int(torch.count_nonzero(y)) < y.numel()
+        leaves = [x16, conv.weight, conv.bias, bn.weight, bn.bias] + ([res] if with_res else [])
+        grad16.reset_stats()
+        grads = torch.autograd.grad(y, leaves, dy)
+        out[name] = (y.detach(),) + tuple(grads), grad16.stats()
+    (a, stats_a), (b, stats_b) = out["grad16"], out["train16"]
+    assert stats_a == stats_b == {"relu_grad": 1, "dgrad": 1, "wgrad": 1, "weights": 1}
+    st = train16.stats()
+    assert st["gated"] == st["premasked"] == st["fallback"] == 0 and train16.pair_adds() == 0
+    names = ["y", "dx", "dW", "d conv.bias", "d gamma", "d beta"] + (["d residual"] if with_res else [])
+    assert len(a) == len(b) == len(names)
+    for what, ta, tb in zip(names, a, b):
+        assert ta.dtype == tb.dtype and ta.shape == tb.shape, what
+        assert torch.equal(ta, tb), what                 # (the strides of dW differ for a 1x1 layer: the values do not)
+    assert bool(torch.isfinite(a[2]).all()) and float(a[2].abs().max()) > 0.0
