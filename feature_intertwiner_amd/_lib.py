@@ -28,7 +28,7 @@ class ConvLaunch(ctypes.Structure):
     """FiConvLaunch of include/fi_capi.h: one planned launch of the fp32 convolution kernels."""
     _fields_ = [(f, ctypes.c_int32) for f in (
         "form", "kernel_id", "tile_rows", "tile_pixels", "window", "flags", "grid_x", "grid_y", "grid_z", "p_base", "pixels",
-        "splits", "pixels_per_split", "per_launch")]
+        "splits", "pixels_per_split", "per_launch", "staging")]
 
 
 _lp = ctypes.POINTER(ConvLaunch)
@@ -210,6 +210,7 @@ def planned_kernel(query, *args):
 FWD_FORMS = ("GENERIC", "PATCH", "PATCH_FLAT13", "PATCH_FLAT14", "WINO14", "WINO", "REG1X1", "RING")
 WGRAD_FORMS = ("VEC", "VEC_TWO_TAP", "SCALAR_TAP_MAJOR", "SCALAR_ROW_MAJOR")
 WINDOWS = ("1x1", "3x3", "7x7", "other")
+WINO_STAGINGS = ("SCALAR", "PAIR")      # FI_WINO_STAGING_*
 LAUNCH_FLAGS = {"tap_major": 1, "channels_last": 2, "vec_out": 4, "swizzled": 8, "row_uniform": 16, "winograd": 32}
 
 

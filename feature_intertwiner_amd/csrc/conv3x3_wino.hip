@@ -37,16 +37,27 @@ struct WinoGeom {
 // 2 output rows x 64 columns; on narrow maps a group wraps rows and spans images) x 128 output channels (4 wavefronts
 // x 32); a wavefront keeps the 16 transform-domain accumulators of its 32 x 32 block (256 registers: one wavefront per
 // SIMD).  Per block of 16 input channels:
-//   V = Bt d B  is computed ONCE per workgroup on the way into LDS (a thread: one tile x two channels, 16 clamped
-//               4-byte loads each -- never an address outside x -- padding selected to zero afterwards), stored
-//               [channel][tile][position] with a tile pitch of 20 floats: a lane's 16 B operands of one channel are four
-//               conflict-free ds_read_b128;
+//   V = Bt d B  is computed ONCE per workgroup on the way into LDS (a thread: one tile x two channels, its 4 x 4 window
+//               read at clamped coordinates -- never an address outside x -- padding selected to zero afterwards),
+//               stored [channel][tile][position] with a tile pitch of 20 floats: a lane's 16 B operands of one channel
+//               are four conflict-free ds_read_b128.  Two stagings, one instantiation each, chosen by plan_forward:
+//                 PAIR    (x 8-byte aligned) 8 read instructions per channel: the centre columns 2tx, 2tx + 1 of a window
+//                         row are one 8-byte load (H and W even: aligned, never clamped in x); the halo columns 2tx - 1
+//                         and 2tx + 2 are the neighbouring tiles' centre values, and the 32 tiles of a group are 32
+//                         consecutive lanes of a wavefront, so they arrive by a DPP wave shift when the value is
+//                         consumed.  Only tile 0 (left) and tile 31 (right) of a group have a halo no lane holds: one
+//                         4-byte load per window row, which every other lane aims at its own centre and drops.  Where
+//                         the neighbouring lane is not the neighbouring tile (a tile row's first / last tile, the
+//                         batch's last tile) the halo is padding and the s_cok select drops what was shifted in.
+//                 scalar  (any x; FI_WINO_SCALAR_STAGING) 16 four-byte loads per channel.
+//               Both stage the same values, so the outputs are the same bit for bit (the first block, staged in front of
+//               the loop, takes the 4-byte loads with either);
 //   U = G g Gt  is computed by every lane from the tap-major weights the direct kernel loads as well (9 x 16 bytes per
 //               half block of 4 channels, double buffered in registers): 28 VALU operations per (cout, cin), in the
 //               shadow of the 16 MFMAs of the channel before.  flip only changes which tap goes where in g.
 // The loop is software pipelined by hand, one channel (16 MFMAs) per step: the LDS reads and the weight transform of
-// step s + 1 sit between the MFMAs of step s, the next block's input loads at step 0, its weight loads at steps 1 and
-// 4, its input transform and LDS stores at steps 5 and 6.
+// step s + 1 sit between the MFMAs of step s, the next block's input loads at step 0 (PAIR: one per slot, scalar: two),
+// its weight loads at steps 1 and 4, its input transform and LDS stores at steps 5 and 6.
 // 128 MFMAs per wavefront and channel block (direct: 288).  An accumulator is a chain over the channels in a fixed
 // order (block by block, pair (k, k + 8) by pair) and the output transform is lane-local, so an output element's
 // arithmetic does not depend on the tile's place in its group or in the batch.
@@ -112,8 +123,8 @@ __device__ __forceinline__ void wino_epilogue(const f32x16 (&acc)[16], const Epi
 }
 
 // H and W even, Cin % 16 == 0 (plan_forward).  FIX: H == W == FIX at compile time (the 14 x 14 RoI maps: the tile decode and
-// the strides fold to constants), 0: H and W from g.
-template <int FIX>
+// the strides fold to constants), 0: H and W from g.  PAIR: the staging (header comment); it needs x 8-byte aligned.
+template <int FIX, bool PAIR>
 __global__ __launch_bounds__(kThreads, 1) void conv3x3_wino_flat_kernel(const float *__restrict__ x,
                                                                        const float *__restrict__ w, Epilogue ep,
                                                                        float *__restrict__ y, WinoGeom g)
@@ -155,7 +166,31 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_wino_flat_kernel(const fl
         s_co[r] = min(max(xx, 0), W - 1);
     }
     const int s_base = (s_n * g.Cin + (tid >> 5)) * HW;              // < 2^31 (patch_eligible)
+    // PAIR, in the loop: raw[i][4 r + 1], [4 r + 2] hold the centre pair of window row r and [4 r] the group-edge value (the
+    // left halo of tile 0, the right halo of tile 31, a dropped re-read of the own centre elsewhere); [4 r + 3] is not used
+    const bool s_t0 = (tid & 31) == 0, s_t31 = (tid & 31) == 31;
+    const int s_ce = s_t0 ? s_co[0] : (s_t31 ? s_co[3] : 2 * s_tx);
     float raw[2][16];
+    auto pair_load = [&](const float *__restrict__ xb, int i, int r) {
+        const float2 v = *reinterpret_cast<const float2 *>(xb + s_base + i * 8 * HW + s_ro[r] + 2 * s_tx);
+        raw[i][4 * r + 1] = v.x;
+        raw[i][4 * r + 2] = v.y;
+    };
+    auto edge_load = [&](const float *__restrict__ xb, int i, int r) {
+        raw[i][4 * r] = xb[s_base + i * 8 * HW + s_ro[r] + s_ce];
+    };
+    // window value (row r, column c) of channel i before the padding select.  PAIR: the halo columns are the centre
+    // values of the lane below (wave_shr:1) / above (wave_shl:1); all 64 lanes are active wherever this runs
+    auto win = [&](int i, int r, int c) -> float {
+        if (!PAIR || c == 1 || c == 2) return raw[i][4 * r + c];
+        const int mine = __builtin_bit_cast(int, raw[i][4 * r + (c == 0 ? 2 : 1)]);
+        const int edge = __builtin_bit_cast(int, raw[i][4 * r]);     // what a lane without a source lane keeps
+        const int theirs = c == 0 ? __builtin_amdgcn_update_dpp(edge, mine, 0x138, 0xf, 0xf, false)
+                                  : __builtin_amdgcn_update_dpp(edge, mine, 0x130, 0xf, 0xf, false);
+        return (c == 0 ? s_t0 : s_t31) ? raw[i][4 * r] : __builtin_bit_cast(float, theirs);
+    };
+    // the first block, in front of the loop: 4-byte loads with either staging (once per workgroup; with the shifts here as
+    // well the <14, PAIR> instantiation spilled 63 registers around the loop)
     auto stage_load = [&](int cb) {
         const float *__restrict__ xb = x + (size_t)cb * BK * HW;
 #pragma unroll
@@ -265,10 +300,12 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_wino_flat_kernel(const fl
         uo[4 * r + 3] = ut[r][2];
     };
     auto scol = [&](int i, int c) {
-        const float d0 = (s_rok[0] && s_cok[c]) ? raw[i][c] : 0.0f;
-        const float d1 = (s_rok[1] && s_cok[c]) ? raw[i][4 + c] : 0.0f;
-        const float d2 = (s_rok[2] && s_cok[c]) ? raw[i][8 + c] : 0.0f;
-        const float d3 = (s_rok[3] && s_cok[c]) ? raw[i][12 + c] : 0.0f;
+        // the wave shifts of win run in front of the selects: with every lane active
+        const float v0 = win(i, 0, c), v1 = win(i, 1, c), v2 = win(i, 2, c), v3 = win(i, 3, c);
+        const float d0 = (s_rok[0] && s_cok[c]) ? v0 : 0.0f;
+        const float d1 = (s_rok[1] && s_cok[c]) ? v1 : 0.0f;
+        const float d2 = (s_rok[2] && s_cok[c]) ? v2 : 0.0f;
+        const float d3 = (s_rok[3] && s_cok[c]) ? v3 : 0.0f;
         sd[0][c] = d0 - d2;
         sd[1][c] = d1 + d2;
         sd[2][c] = d2 - d1;
@@ -311,8 +348,16 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_wino_flat_kernel(const fl
                         ucol(ga, 0, q >> 1);                         // step 0 of the next block
                 }
                 if (q == 7 || q == 9 || q == 11 || q == 13) urow(u[(s + 1) & 1], (q - 7) >> 1);
-                // the next block's input: 32 loads at step 0, transformed and stored at steps 5 and 6 (even slots)
-                if (s == 0) {
+                // the next block's input: 16 (PAIR) or 32 loads at step 0, transformed and stored at steps 5 and 6 (even
+                // slots)
+                if (s == 0 && PAIR) {
+                    const int i = q >> 3, r = q & 3;
+                    if (q & 4)
+                        edge_load(xn, i, r);
+                    else
+                        pair_load(xn, i, r);
+                }
+                if (s == 0 && !PAIR) {
                     const int e0 = 2 * (q & 7), i = q >> 3;
                     raw[i][e0] = xn[s_base + i * 8 * HW + s_ro[e0 >> 2] + s_co[e0 & 3]];
                     raw[i][e0 + 1] = xn[s_base + i * 8 * HW + s_ro[e0 >> 2] + s_co[(e0 & 3) + 1]];
@@ -356,7 +401,8 @@ void launch_conv3x3_wino_flat(const WinoArgs &a, hipStream_t st)
     g.mtiles = ceil_div(a.Cout, 128);
     g.zero = a.zero;
     const Epilogue ep = {a.bias, a.scale, a.residual, a.relu, a.gate};
-    auto k = a.hw14 ? conv3x3_wino_flat_kernel<WINO_HW> : conv3x3_wino_flat_kernel<0>;
+    auto k = a.hw14 ? (a.pair ? conv3x3_wino_flat_kernel<WINO_HW, true> : conv3x3_wino_flat_kernel<WINO_HW, false>)
+                    : (a.pair ? conv3x3_wino_flat_kernel<0, true> : conv3x3_wino_flat_kernel<0, false>);
     hipLaunchKernelGGL(k, dim3((unsigned)a.grid), dim3(kThreads), 0, st, a.x, a.w, ep, a.y, g);
 }
 

@@ -2042,6 +2042,9 @@ int plan_forward(ConvGeom &g, FwdPlan &p, const float *x, const float *weight, c
             l.form = FI_FWD_WINO;
         const bool wino = l.form == FI_FWD_WINO14 || l.form == FI_FWD_WINO;
         if (wino) l.flags &= ~FI_LAUNCH_VEC_OUT;
+        // its input staging: centre pairs by 8-byte loads and halos from the neighbouring lanes where x is 8-byte aligned
+        // (the flat rule asks for that, the 2-D rule does not); FI_WINO_SCALAR_STAGING keeps the 4-byte loads
+        if (wino && (uintptr_t)x % 8 == 0 && !getenv("FI_WINO_SCALAR_STAGING")) l.staging = FI_WINO_STAGING_PAIR;
         // both kernels: an XCD-banded 1-D grid, the pixel tiles (Winograd: groups of WINO_GROUP 2 x 2 tiles) padded to 8
         l.grid_x = fi::ceil_div(wino ? fi::ceil_div(N * (H / 2) * (W / 2), fi::WINO_GROUP) : ptiles, 8) * 8 * mtiles;
     } else if (reg1x1) {
@@ -2532,7 +2535,7 @@ int fi_conv2d_forward_live(const float *x, const float *weight, const float *bia
     case FI_FWD_WINO14:
     case FI_FWD_WINO: {
         const fi::WinoArgs wa = {x, weight, bias, scale, residual, gate, y, g.zero, N, Cin, H, W, Cout, relu, g.flip,
-                                 l.form == FI_FWD_WINO14, l.grid_x};
+                                 l.form == FI_FWD_WINO14, l.grid_x, l.staging == FI_WINO_STAGING_PAIR};
         fi::launch_conv3x3_wino_flat(wa, st);
         break;
     }

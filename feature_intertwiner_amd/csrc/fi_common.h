@@ -30,7 +30,7 @@ struct RingArgs {
 int launch_conv1x1_ring(const RingArgs &a, hipStream_t st);
 
 // conv3x3_wino.hip (launched by fi_conv2d_forward_live when plan_forward picks the Winograd form of a patch slot, flat or
-// 2-D): any NCHW map with even H and W, y / residual / gate 8-byte aligned
+// 2-D): any NCHW map with even H and W, y / residual / gate 8-byte aligned; x 8-byte aligned for the PAIR staging
 constexpr int WINO_HW = 14;          // H == W == 14 (the RoI maps, 7 x 7 tiles of 2 x 2 pixels) keeps a compile-time instantiation
 constexpr int WINO_GROUP = 32;       // 2 x 2 tiles per workgroup
 struct WinoArgs {
@@ -39,7 +39,8 @@ struct WinoArgs {
     const float *zero;
     int N, Cin, H, W, Cout, relu, flip;
     int hw14;                        // the plan's choice: the WINO_HW instantiation (FI_FWD_WINO14), else H and W at run time
-    int grid;                        // ... and its grid
+    int grid;                        // ... its grid
+    int pair;                        // ... and its staging: FI_WINO_STAGING_PAIR (x 8-byte aligned), else 4-byte loads only
 };
 void launch_conv3x3_wino_flat(const WinoArgs &a, hipStream_t st);
 

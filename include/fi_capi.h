@@ -496,7 +496,12 @@ int fi_gemm_nt_plan(const float *a, const float *b, const float *scale, const fl
  *                      aligned, at least 256 tiles of 128 pixels x 128 channels: conv1x1_reg_kernel
  *   FI_FWD_GENERIC     everything else: conv_fwd_kernel<tile_rows, window, tap-major, channels-last, tile_pixels>
  * (FI_NO_PATCH, FI_NO_REG1X1, FI_NO_WINOGRAD in the environment, read per call, switch the patch, register and Winograd forms
- * off.)  The generic form alone has further choices:
+ * off.)  The Winograd forms stage their input one of two ways, named by `staging` (the form, key and counter are the same):
+ *   FI_WINO_STAGING_PAIR    x 8-byte aligned: per window row one 8-byte load of the two centre columns, the halo columns
+ *                           from the neighbouring lanes, one 4-byte load for the edges of a group of 32 tiles
+ *   FI_WINO_STAGING_SCALAR  any other x, or FI_WINO_SCALAR_STAGING in the environment (read per call): 4-byte loads only;
+ *                           the same results bit for bit
+ * The generic form alone has further choices:
  *   tile_rows    64 for Cout <= 64 or fewer than 512 tiles of 128 pixels x 128 channels, else 128
  *   tile_pixels  64 on 64-row tiles of a tap-major NCHW launch with fewer than 1024 workgroups and at least 64 pixels, else 128
  *   main / tail  a tap-major NCHW launch of T > 1024 tiles of 128 x 128 with 0 < 3 (T mod 1024) < 1024 and a tile-row count
@@ -549,6 +554,7 @@ enum {
     FI_WGRAD_SCALAR_ROW_MAJOR = 3
 };
 enum { FI_WIN_1X1 = 0, FI_WIN_3X3 = 1, FI_WIN_7X7 = 2, FI_WIN_OTHER = 3 };      /* run-time R x S */
+enum { FI_WINO_STAGING_SCALAR = 0, FI_WINO_STAGING_PAIR = 1 };
 enum {
     FI_LAUNCH_TAP_MAJOR = 1,         /* forward: weights [Cout][R][S][Cin]; weight gradient: dW in that layout */
     FI_LAUNCH_CHANNELS_LAST = 2,     /* forward: y is [N][OH][OW][Cout] */
@@ -566,6 +572,7 @@ typedef struct {
     int32_t grid_x, grid_y, grid_z;
     int32_t p_base, pixels;          /* forward: the launch computes output pixels [p_base, p_base + pixels) */
     int32_t splits, pixels_per_split, per_launch;      /* weight gradient */
+    int32_t staging;                 /* FI_FWD_WINO14 / FI_FWD_WINO: FI_WINO_STAGING_*; 0 for every other form */
 } FiConvLaunch;
 /* The launches fi_conv2d_forward_live makes for these arguments (no live count): *n of them, 1 or 2, in out[0 .. *n).
  * Host-only like fi_conv2d_forward_plan: same checks, same status, nothing dereferenced, nothing launched. */

@@ -26,31 +26,40 @@ run("mask 14x14 256 N1376", 1376, 256, 14, 14, 256, "conv3x3_patch_flat")
 run("mask 14x14 256 N672", 672, 256, 14, 14, 256, "conv3x3_patch_flat")
 
 
-def run_flat(name, N, Cin, Cout=256, H=14, W=14, key="conv3x3_patch_flat", rounds=5, iters=8):
-    """A patch slot (flat or 2-D) with its Winograd form and with FI_NO_WINOGRAD=1 (the library reads the switch per call),
-    rounds of the two interleaved in this process on the same random data: median and min us per variant, TFLOP/s in
-    direct-form flops (the Winograd form issues 16/36 of the MFMAs, so its figure may read above the MFMA peak).  On a shape
-    the planner keeps on the direct kernel the two variants are the same launch and the speed-up reads 1."""
+def run_flat(name, N, Cin, Cout=256, H=14, W=14, key="conv3x3_patch_flat", rounds=5, iters=8, flip=False):
+    """A patch slot (flat or 2-D) three ways -- its Winograd form with the planned input staging, the same with
+    FI_WINO_SCALAR_STAGING=1 (4-byte loads only) and the direct kernel (FI_NO_WINOGRAD=1); the library reads both switches per
+    call -- in rounds of the three interleaved in this process on the same random data: median, min and spread (max - min) in
+    us per variant, TFLOP/s in direct-form flops (the Winograd form issues 16/36 of the MFMAs, so its figure may read above
+    the MFMA peak).  flip: the data gradient (tap-major weights applied in reverse order).  On a shape the planner keeps on
+    the direct kernel the variants are the same launch and the ratios read 1."""
     x = torch.randn(N, Cin, H, W, device=DEV)
     w = (torch.randn(Cout, Cin, 3, 3, device=DEV) * 0.05).contiguous(memory_format=torch.channels_last)
+    if flip: w = w.permute(0, 2, 3, 1).contiguous()
     sc = torch.rand(Cout, device=DEV) + 0.5; b = torch.randn(Cout, device=DEV)
-    us = {"winograd": [], "direct": []}
+    kw = dict(w_tap_major=True, flip_taps=True) if flip else {}
+    switch = {"winograd": None, "winograd_scalar_staging": "FI_WINO_SCALAR_STAGING", "direct": "FI_NO_WINOGRAD"}
+    us = {v: [] for v in switch}
     for r in range(rounds + 1):
-        for variant in ("winograd", "direct"):
-            if variant == "direct": os.environ["FI_NO_WINOGRAD"] = "1"
-            else: os.environ.pop("FI_NO_WINOGRAD", None)
+        for variant, env in switch.items():
+            for e in switch.values():
+                if e: os.environ.pop(e, None)
+            if env: os.environ[env] = "1"
             torch.cuda.synchronize(); _lib.prof_reset(); _lib.prof_enable(True)
-            for _ in range(iters): _conv_fwd(x, w, b, (1, 1), (1, 1), relu=True, scale=sc)
+            for _ in range(iters): _conv_fwd(x, w, b, (1, 1), (1, 1), relu=True, scale=sc, **kw)
             torch.cuda.synchronize(); _lib.prof_enable(False)
             n, ms = _lib.prof_get(key); assert n == iters, (n, iters)
             if r: us[variant].append(ms / n * 1e3)                 # round 0 warms up
-    os.environ.pop("FI_NO_WINOGRAD", None)
+    for e in switch.values():
+        if e: os.environ.pop(e, None)
     fl = 2.0 * N * H * W * Cin * Cout * 9; out = {"layer": name}
     for variant, v in us.items():
         v.sort(); med = v[len(v) // 2]
-        out[variant] = {"us_median": round(med, 1), "us_min": round(v[0], 1), "TFLOPs_direct_form": round(fl / med / 1e6, 1)}
+        out[variant] = {"us_median": round(med, 1), "us_min": round(v[0], 1), "us_spread": round(v[-1] - v[0], 1),
+                        "TFLOPs_direct_form": round(fl / med / 1e6, 1)}
     out["speedup_median"] = round(out["direct"]["us_median"] / out["winograd"]["us_median"], 3)
-    print(json.dumps(out))
+    out["ratio_scalar_staging_over_winograd"] = round(out["winograd_scalar_staging"]["us_median"] / out["winograd"]["us_median"], 3)
+    print(json.dumps(out), flush=True)
 
 
 for n_img in (1376, 672):
@@ -64,3 +73,6 @@ for name, N, Cin, H, W, Cout in (("C4 / P4 64x64 256->256 N4 (256)", 4, 256, 64,
                                  ("FPN P2 256x256 256->256 N4 (4096)", 4, 256, 256, 256, 256),
                                  ("RPN P2 256x256 256->512 N4 (8192)", 4, 256, 256, 256, 512)):
     run_flat(name, N, Cin, Cout, H, W, key="conv3x3_patch")
+# the data gradient (taps reversed) of one layer of each slot
+run_flat("mask 14x14 256->256 N1376 dgrad", 1376, 256, flip=True)
+run_flat("FPN P2 256x256 256->256 N4 (4096) dgrad", 4, 256, 256, 256, 256, key="conv3x3_patch", flip=True)
